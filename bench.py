@@ -2,6 +2,7 @@
 """Benchmark of the exact top-k search engine (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c3b1|c2]
+                    [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one batch of queries: scan of the
 whole (row-sharded) corpus, fused per-GPU top-k, RCCL all-gather of the local
@@ -14,8 +15,16 @@ on a 10M x 768 corpus with top-10): 10,000,000 x 768 bf16 synthetic unit rows,
 fixed and row-sharded over the N GPUs; value = queries/s of the whole job.
 
 Prints ONE JSON line on rank 0 (driver contract), with "roofline" for the
-dominant kernel (HIP-event durations on the engine's stream) and
-"cpu_baseline" (oracle/ CPU scan timed on this host, rank 0, N = 1 only).
+dominant kernel (HIP-event durations on the engine's stream, taken inside the
+timed steps themselves).
+
+A plain run does what the headline figure needs and no more: set-up, warm-up,
+the timed steps, --dump-outputs, the line. --full adds, after the timed
+region, everything else this file measures or checks: the per-step result
+checks ("steps_verified"), the single-query line on the same corpus
+("secondary"), the same batches on the bf16 / f32 pass alone
+("<dtype>_pass"), "cpu_baseline" (oracle/ CPU scan timed on this host, rank
+0, N = 1 only) and the oracle "parity" of the timed batches.
 """
 from __future__ import annotations
 
@@ -90,14 +99,22 @@ def parse():
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--rows", type=int, default=0, help="override corpus rows (testing only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the result checks, the secondary "
+                         "lines, the CPU baselines and the oracle parity")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave out the CPU baselines and the oracle parity")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="with --full: leave out the secondary GPU lines")
     ap.add_argument("--cpu-sample-rows", type=int, default=0,
                     help="CPU baseline corpus rows (0 = the full corpus)")
     ap.add_argument("--cpu-budget-s", type=float, default=12.0,
                     help="time budget of each CPU baseline leg (per-query scan, batched BLAS)")
     ap.add_argument("--dump-keys", default="",
                     help="rank 0 writes the last step's merged keys here (.npy; parity tests)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the last timed step returned to DIR/scores.npy "
+                         "(float32), DIR/rows.npy and DIR/counts.npy (float64)")
     a = ap.parse_args()
     one = CONFIGS[a.config][4] == 1
     if a.steps is None:
@@ -302,6 +319,21 @@ def verify_steps(pkg, outs, k, n_rows, sharded=None, qs=None, recheck=(0, -1)):
             if not np.array_equal(again.cpu().numpy(), outs[i].cpu().numpy()):
                 raise AssertionError(f"timed step {i}: a second search of its batch differs")
     return len(outs)
+
+
+def dump_outputs(pkg, out, dirname):
+    """What a caller of the timed path receives from its last step -- the
+    merged key list of every query of the batch -- decoded (engine.keys_decode)
+    into scores.npy (B x k float32, descending), rows.npy (B x k row ids as
+    float64: ids are < 2^32, exact) and counts.npy (B valid entries per query,
+    float64). The corpus, the query stream and the batch each step searches
+    depend only on the arguments, so two builds run with the same arguments
+    are compared array for array."""
+    s, r, c = pkg.keys_decode(out.cpu().numpy().view(np.uint64))
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "scores.npy"), np.ascontiguousarray(s, np.float32))
+    np.save(os.path.join(dirname, "rows.npy"), r.astype(np.float64))
+    np.save(os.path.join(dirname, "counts.npy"), c.astype(np.float64))
 
 
 def oracle_parity(pkg, cfg, n_full, outs, batch, row0, picks):
@@ -529,7 +561,10 @@ def main():
                                  dist_on, stream_fn, 0, coll if int8_pre else None)
     spec = tm.get("spec")
     out = outs[-1]
-    steps_verified = verify_steps(pkg, outs, k, n_full, sharded, qs)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(pkg, out, args.dump_outputs)
+    # everything below the timed steps that is not the line itself: --full only
+    steps_verified = verify_steps(pkg, outs, k, n_full, sharded, qs) if args.full else None
     elem = 2 if dtype == "bf16" else 4
     # batched bf16 searches of a collection with an int8 copy run the int8
     # prefilter pass (the engine's default; VS_FLAG_NO_PREFILTER turns it off)
@@ -575,7 +610,7 @@ def main():
     }
 
     # secondary: the single-query GEMV line on the same resident corpus
-    if not args.no_secondary and batch > 1:
+    if args.full and not args.no_secondary and batch > 1:
         # 160+ single-query steps after 10 of warmup: at ~1.3 ms each the line
         # costs a fifth of a second, and its sampled kernel average (every 16th
         # launch) rests on 10+ launches
@@ -592,7 +627,7 @@ def main():
 
     # secondary (one GPU): the same batch on the bf16 / f32 pass alone -- a
     # second engine without the int8 copy over the same generated rows
-    if int8 and world == 1 and not dist_on and not args.no_secondary:
+    if args.full and int8 and world == 1 and not dist_on and not args.no_secondary:
         eng.drop_collection(coll)  # room for the second corpus
         e2 = pkg.VectorEngine(device=local, timing=True, timing_sample=sample, prefilter=False)
         try:
@@ -619,7 +654,7 @@ def main():
         finally:
             e2.close()
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             result["cpu_baseline"] = cpu_baseline(cfg, args, n_full)
         except Exception as e:  # the baseline never decides the run

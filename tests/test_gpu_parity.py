@@ -360,8 +360,8 @@ def test_bench_small_runs():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     for cfg in ("c3", "c2"):
-        res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", cfg,
-                              "--rows", "300000", "--steps", "3", "--warmup", "1",
+        res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full",
+                              "--config", cfg, "--rows", "300000", "--steps", "3", "--warmup", "1",
                               "--cpu-sample-rows", "20000", "--cpu-budget-s", "0.5"],
                              capture_output=True, text=True, timeout=300)
         assert res.returncode == 0, res.stderr[-3000:]

@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""Copies a measure_round.sh batch from gpurun_out/ into profiles/ (tracked):
+"""Copies a measure_round.sh batch from its $OUT (default bench_out/) into profiles/ (tracked):
 the bench lines, the rocprofv3 kernel stats and the main-pass per-launch
 trace named with the benched binary's build id, C1 and the concurrency
 trials; prints the bench's kernel_ms beside the trace's post-warmup mean.
 
-    python tools/collect_round.py TAG
+    [OUT=DIR] python tools/collect_round.py TAG
 """
 import csv
 import json
@@ -14,7 +14,7 @@ import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-G = os.path.join(ROOT, "gpurun_out")
+G = os.environ.get("OUT") or os.path.join(ROOT, "bench_out")
 P = os.path.join(ROOT, "profiles")
 
 

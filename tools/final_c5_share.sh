@@ -13,5 +13,5 @@ timeout -k 10 300 python bench.py $B > gpurun_out/fin_share.json 2> gpurun_out/f
 env VS_DIST_BACKEND=nccl VS_BENCH_FORCE_DIST=1 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 \
   --nproc-per-node=1 --master-addr 127.0.0.1 --master-port $((29500 + RANDOM % 1000)) bench.py $B \
   > gpurun_out/fin_share_rccl1.json 2> gpurun_out/fin_share_rccl1.err || exit 1
-timeout -k 10 400 python bench.py --config c4 --rows 12500000 --steps 30 --warmup 5 --no-cpu-baseline \
+timeout -k 10 400 python bench.py --full --config c4 --rows 12500000 --steps 30 --warmup 5 --no-cpu-baseline \
   > gpurun_out/fin_c4share.json 2> gpurun_out/fin_c4share.err || exit 1

@@ -11,7 +11,7 @@ and the step span; so "outside the main pass" = span - main pass is read off
 directly. Kernels of the CPU-side setup (generate,
 quantize) fall outside the steps and are ignored. --with NAME keeps only the
 steps that launch a kernel whose short name contains NAME, --without NAME
-drops those that do (bench.py's run
+drops those that do (a `bench.py --full` run
 holds the main line's steps, then the secondary line's and the bf16_pass
 line's: `--with true>` picks the int8 pass's, `mfma<768,0,2304,2,false,false>`
 the bf16 pass's).
