@@ -17,48 +17,9 @@ import pytest
 D = 768
 
 
-def _up(v):
-    return np.nextafter(np.float32(v), np.float32(np.inf))
-
-
-def _quantize_rows(X, S):
-    X8 = np.clip(np.rint(X / S), -127, 127).astype(np.int32)
-    d = X.astype(np.float64) - np.float64(S) * X8
-    dn = np.sqrt((d * d).sum(1)) * (1 + 2.0 ** -30)
-    xn = np.sqrt((X.astype(np.float64) ** 2).sum(1)) * (1 + 2.0 ** -30)
-    dt = np.array([_up(dn[i:i + 32].max()) for i in range(0, len(X), 32)], np.float32)
-    nt = np.array([_up(xn[i:i + 32].max()) for i in range(0, len(X), 32)], np.float32)
-    return X8, dt, nt
-
-
-def _quantize_query(q, S):
-    amax = np.float32(np.abs(q).max())
-    sq = np.float32(amax / np.float32(127)) if amax > 0 else np.float32(0)
-    q8 = np.clip(np.rint(q / sq), -127, 127).astype(np.int32) if sq > 0 else np.zeros(D, np.int32)
-    s = np.float64(sq) * q8
-    a = _up(np.sqrt((s * s).sum()) * (1 + 2.0 ** -30))
-    e = q.astype(np.float64) - s
-    c = _up(np.sqrt((e * e).sum()) * (1 + 2.0 ** -30))
-    nq = _up(np.sqrt((q.astype(np.float64) ** 2).sum()) * (1 + 2.0 ** -30))
-    sigma = np.float32((4.0 * D + 64.0) * 2.0 ** -24 * float(nq) * (1 + 2.0 ** -20))
-    return q8, np.float32(sq * np.float32(S)), a, c, sigma
-
-
-def _fp32_sums(X, q):
-    """fp32 scores in three orders: sequential, pairwise (numpy), reversed."""
-    xf, qf = X.astype(np.float32), q.astype(np.float32)
-    seq = np.zeros(len(X), np.float32)
-    rev = np.zeros(len(X), np.float32)
-    for i in range(D):
-        seq = np.float32(seq + xf[:, i] * qf[i])
-        rev = np.float32(rev + xf[:, D - 1 - i] * qf[D - 1 - i])
-    return [seq, rev, (xf @ qf).astype(np.float32)]
-
-
-def _bf16(a):
-    u = np.ascontiguousarray(a, np.float32).view(np.uint32)
-    u = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
-    return u.view(np.float32)
+# the restatement itself lives in tests/q8_ref.py, shared with the GPU stage tests
+from q8_ref import (QUERY_KINDS, _bf16, _fp32_sums, _quantize_query, _quantize_rows, _up,  # noqa: F401
+                    bracket, make_queries, make_rows, row_kinds, scale_of)
 
 
 @pytest.mark.parametrize("case", ["unit_bf16", "fp32", "clipped", "spiky"])
@@ -110,3 +71,52 @@ def test_int8_window_is_narrow():
     m = float(a * dt.max() + c * nt.max())
     spread = float(np.std(X.astype(np.float64) @ q.astype(np.float64)))
     assert 0.2 < 2 * m / spread < 1.5, (m, spread)
+
+
+def _cases():
+    for f32 in (False, True):
+        for kind in row_kinds(f32):
+            for dim in (768, 1024) if not f32 else (768,):
+                yield pytest.param(kind, f32, dim, id=f"{kind}-{'f32' if f32 else 'bf16'}-{dim}")
+    yield pytest.param("unit", False, 128, id="unit-bf16-128")
+    # (the bracket's domain ends at dim 127^2 < 2^24, dim <= 1040: DESIGN.md §5 "Domain")
+    yield pytest.param("clipped", True, 1024, id="clipped-f32-1024")
+    yield pytest.param("pm_absmax", True, 1024, id="pm_absmax-f32-1024")
+
+
+@pytest.mark.parametrize("kind,f32,dim", list(_cases()))
+def test_reference_bracket_on_every_generator(kind, f32, dim):
+    """Every row kind x every query kind the GPU stage tests use: the
+    reference bracket L <= s <= U holds against the fp64 score and against
+    fp32 sums in three orders, with a stale S where the kind has one and a
+    ragged last tile (n = 101)."""
+    n = 101
+    X, X0 = make_rows(kind, n, dim, f32)
+    assert X.shape == (n, dim) and (f32 or np.all(_bf16(X) == X))
+    S = scale_of(X0)
+    X8, dt, nt = _quantize_rows(X, S)
+    assert X8.min() >= -127 and X8.max() <= 127
+    if kind == "pm_absmax":
+        assert np.all(np.abs(X8) == 127)
+    if kind == "halfway":  # rint went to even on every value but the planted absmax
+        assert np.all(X8.ravel()[1:] % 2 == 0)
+    if kind == "tiny":
+        assert np.all(X8[1::2] == 0)
+    Q, kinds = make_queries(X, f32)
+    assert kinds == QUERY_KINDS
+    tile = np.arange(n) // 32
+    for q, qk in zip(Q, kinds):
+        assert f32 or np.all(_bf16(q) == q)
+        q8, sqS, a, c, sigma = _quantize_query(q, S)
+        dot = X8 @ q8
+        assert np.abs(dot).max() < 2 ** 24, (kind, qk)  # exact in fp32 too
+        L, U = bracket(dot, sqS, a, c, sigma, dt[tile], nt[tile])
+        exact = X.astype(np.float64) @ q.astype(np.float64)
+        assert np.all(L <= exact) and np.all(exact <= U), (kind, qk)
+        for s in _fp32_sums(X, q):
+            assert np.all(L <= s) and np.all(s <= U), (kind, qk)
+        if qk == "zero":
+            assert sqS == 0 and a == 0 and c == 0 and sigma == 0 and not q8.any()
+    if kind == "pm_absmax" and dim == 1024:  # the largest dot the int8 pass can meet
+        q8 = _quantize_query(Q[kinds.index("pm_amax")], S)[0]
+        assert abs(int(X8[0] @ q8)) == 127 * 127 * dim

@@ -2,6 +2,10 @@
 // host computation (r04): quantisation (x8, tile bounds), int8 queries and
 // their bounds, the int8 MFMA pass's dots (every slab admitted: no bound),
 // and that each row's fp32 score lies inside [L, U].
+// The host check (no arguments) is one shape on benign rows; the suite holds
+// the same checks on adversarial rows at the shapes where the kernels can go
+// wrong (tests/test_q8_stages_gpu.py). The stats mode is what DESIGN.md cites.
+// The int8 pass's counts are query-major ([query][wg][4], r05).
 //   hipcc --offload-arch=gfx950 -O2 -std=c++17 tools/q8_check.hip -o tools/q8_check \
 //     -I<pkg>/csrc -L<pkg>/lib -lvsearch -Wl,-rpath,<pkg>/lib
 #include <hip/hip_runtime.h>
@@ -81,7 +85,7 @@ int stats_mode(uint32_t n, uint32_t nq, uint32_t dim, uint32_t k) {
   for (uint32_t w = 0; w < nwg; ++w)
     for (uint32_t q = 0; q < nq; ++q)
       for (uint32_t kq = 0; kq < 4; ++kq) {
-        const uint32_t c = hc[((size_t)w * 256 + q) * 4 + kq];
+        const uint32_t c = hc[((size_t)q * nwg + w) * 4 + kq];
         tot += c;
         qmax = std::max<uint64_t>(qmax, c);
       }
@@ -179,7 +183,7 @@ int main(int argc, char** argv) {
   for (uint32_t q = 0; q < nq; ++q) {
     for (uint32_t w = 0; w < nwg; ++w)
       for (uint32_t kq = 0; kq < 4; ++kq) {
-        const uint32_t c = hc[((size_t)w * 256 + q) * 4 + kq];
+        const uint32_t c = hc[((size_t)q * nwg + w) * 4 + kq];
         for (uint32_t j = 0; j < c; ++j) {
           const size_t e = ((size_t)w * 256 + q) * cap + kq * (cap / 4) + j;
           for (int b = 0; b < 8; ++b) {
@@ -230,7 +234,7 @@ int main(int argc, char** argv) {
   for (uint32_t q = 0; q < nq; ++q) {
     uint64_t tot = 0;
     for (uint32_t w = 0; w < nwg; ++w)
-      for (uint32_t kq = 0; kq < 4; ++kq) tot += hc[((size_t)w * 256 + q) * 4 + kq];
+      for (uint32_t kq = 0; kq < 4; ++kq) tot += hc[((size_t)q * nwg + w) * 4 + kq];
     std::printf("q %u sample bound %g slabs %llu\n", q, hb[q], (unsigned long long)tot);
   }
   std::printf("gate after int8 pass %u\n", hgate);
@@ -240,7 +244,7 @@ int main(int argc, char** argv) {
     int mn = INT_MAX, mxall = INT_MIN;
     for (uint32_t w = 0; w < nwg; ++w)
       for (uint32_t kq = 0; kq < 4; ++kq) {
-        const uint32_t c = hc[((size_t)w * 256 + q) * 4 + kq];
+        const uint32_t c = hc[((size_t)q * nwg + w) * 4 + kq];
         for (uint32_t j = 0; j < c; ++j) {
           const size_t e = ((size_t)w * 256 + q) * cap + kq * (cap / 4) + j;
           int m = INT_MIN;
