@@ -1680,17 +1680,6 @@ __device__ __forceinline__ void glds16(const void* sbase, uint32_t voff, uint32_
         : "memory");
 }
 
-// Ablation only (MODE 11): the same LDS-DMA instruction moving 4 B per lane.
-__device__ __forceinline__ void glds4(const void* sbase, uint32_t voff, uint32_t lds) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-      "global_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(voff), "s"(sbase), "s"(lds)
-      : "memory");
-}
-
 __device__ __forceinline__ uint64_t shfl64(uint64_t v, int src) {
   const uint32_t lo = __shfl((unsigned)(uint32_t)v, src, 64);
   const uint32_t hi = __shfl((unsigned)(uint32_t)(v >> 32), src, 64);
@@ -1848,10 +1837,6 @@ template <bool B>
 struct MfFull {
   static constexpr bool value = B;
 };
-template <int V>
-struct MfSet {
-  static constexpr int value = V;
-};
 
 // Byte geometry of the streamed rows (EB = element bytes: 2 bf16, 4 fp32).
 // A step is 64 bytes of a row: 32 k of bf16 (one 16x16x32 MFMA per row half
@@ -1861,7 +1846,7 @@ template <int D, int RING = kMfRingBytes, int TAIL = kMfListBytes, int WAVES = 8
 struct MfShape {
   static constexpr int RBY = D * EB;                      // bytes per row
   static constexpr int T = RBY / 64;                      // 64-B MFMA steps per row
-  // 128-B pieces per row per chunk (CSX overrides: ablation of chunk sizes)
+  // 128-B pieces per row per chunk (CSX overrides: 6 = the 24 KiB chunks of VAR 2048)
   static constexpr int CS4 = CSX ? CSX : ((RBY % 512 == 0) ? 4 : 2);
   static constexpr int CT = CS4 * 2;                      // steps per chunk
   static constexpr int CPT = RBY / (128 * CS4);           // chunks per 32-row tile
@@ -1879,29 +1864,33 @@ struct MfShape {
 };
 
 // MODE: 0 = main pass (candidate buffers), 3 = sample pass (tile maxima), 8 =
-// main pass with sorted lists (overflow fallback). Ablation builds only
-// (tools/ablate_mfma.hip): 1 = no top-k epilogue, 2 = LDS-DMA stream only,
-// 4 = MFMA + LDS reads + barriers with no DMA, 5 = 4 without barriers, 6 =
-// threshold filter only (never keeps a row), 7 = 1 with one A-fragment read
-// per chunk, 10 = 1 reading only half the A fragments (the compiler then
-// merges the two row halves' MFMA chains: invalid as a timing), 11 = 1 with
-// 4-B LDS-DMA (a quarter of the bytes, same instructions), 13 = 1 with half
-// the A-fragment reads and every MFMA kept (r02: -5.5% against 1; a K-split
-// of query pairs that would halve the reads in the product needed 32
-// accumulator VGPRs and spilled, and its spill-free form needs a shorter
-// ring, which cost +2.4%: not kept). VAR 32 / 64: A fragments read 2 / 3 steps ahead instead of 1;
-// VAR 128: each step's reads and MFMAs pinned in program order; VAR 512:
-// the chunk's LDS-DMA pieces spread over its steps instead of at its head;
-// VAR 1024: flips the corpus stream's load policy (MODE 0 default: non-temporal
-// LDS-DMA; other modes: default policy). VAR 131072 (MODE 0): append counters
-// in LDS instead of registers (the r01-v13 form).
+// main pass with sorted lists (overflow fallback). The decomposition arms
+// that attribute a pass's time (tools/ablate_*.hip only; they write no
+// answers): 1 = no top-k epilogue, 2 = LDS-DMA stream only, 4 = MFMA + LDS
+// reads + barriers with no DMA, 5 = 4 without barriers, 6 = threshold test
+// only (never keeps a row). Every mode that streams streams as the product.
+// VAR (a bit set; any other bit fails to compile): 256 = a 144 KiB ring
+// (not MODE 8, whose lists need the room), 2048 = 24 KiB K-chunks (D = 768);
+// the library runs 0 or 256 + 2048 (mf_product_var, launch_mfma_cand_q8).
+// Tools only: 8192 = per-workgroup clocks into a.lists, 16777216 = the int8
+// pass never appends (a timing arm: wrong answers). The experiments that
+// were measured and taken out of this kernel are listed in DESIGN.md
+// ("Experiments removed from the MFMA scan").
 // F32: fp32 rows and queries on v_mfma_f32_16x16x4_f32 (exact f32 products,
 // fp32 accumulation; 1/16 of the bf16 rate, so the pass is MFMA-bound): same
 // stream, layout and epilogue, a step's 16-B fragment holding 4 k of each
 // lane's k-quarter, consumed by four MFMAs.
+constexpr bool mf_mode_known(int mode) {
+  return mode == 0 || mode == 3 || mode == 8 || mode == 1 || mode == 2 || mode == 4 || mode == 5 ||
+         mode == 6;
+}
+constexpr bool mf_var_known(int var) { return (var & ~(256 | 2048 | 8192 | 16777216)) == 0; }
+
 template <int D, int MODE = 0, int VAR = 0, int G = mf_groups(D), bool F32 = false, bool I8 = false>
 __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_waves(G)) void mfma_topk_kernel(
     const MfArgs a) {
+  static_assert(mf_mode_known(MODE), "MODE: 0, 3, 8 (product) or 1, 2, 4, 5, 6 (decomposition)");
+  static_assert(mf_var_known(VAR), "VAR: only bits 256, 2048, 8192 and 16777216 exist");
   constexpr int WAVES = mf_waves(G), THREADS = 64 * WAVES, QPW = 16 * G;
   constexpr int EB = F32 ? 4 : (I8 ? 1 : 2);
   static_assert(!I8 || (!F32 && (MODE == 0 || MODE == 1 || MODE == 6)), "int8: the main pass only");
@@ -1912,32 +1901,21 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
                 "B fragments must fit the register budget");
   // VAR 256: a 144 KiB ring (more chunks in flight); LDS lists only in MODE 8
   constexpr bool kBigRing = (VAR & 256) != 0 && MODE != 8;
-  // VAR 2048 / 4096: 24 / 48 KiB K-chunks (384 / 768 k of 32 rows) at D = 768
-  constexpr int kCsx = (VAR & 4096) ? 12 : ((VAR & 2048) ? 6 : 0);
-  // candidate passes keep each lane's per-group append counters in LDS (a
-  // register each would push the kernel past 256 VGPRs, and the compiler
-  // then drops the A-fragment prefetch of the streaming loop: r01)
-  // VAR 131072 (ablation): counters in LDS, and each lane's running quarter
-  // maximum beside them (a second set), so cand_max is written in that form too
-  constexpr bool kLdsCnt = MODE == 0 && (VAR & 131072) != 0;
-  constexpr int kCntBytes = MODE == 0 ? 64 * WAVES * G * 4 * (kLdsCnt ? 2 : 1) : 0;
+  // VAR 2048: 24 KiB K-chunks (384 k of 32 bf16 rows) at D = 768
+  constexpr int kCsx = (VAR & 2048) ? 6 : 0;
+  // the main pass's LDS words beside the ring: one per lane and query group,
+  // the lane's running quarter maximum (mf_quarter_max)
+  constexpr int kCntBytes = MODE == 0 ? 64 * WAVES * G * 4 : 0;
   using S = MfShape<D, kBigRing ? 144 * 1024 : kMfRingBytes,
                     MODE == 8 ? kMfListBytes : 16 + kCntBytes, WAVES, kCsx, EB>;
-  constexpr bool kDma = MODE != 4 && MODE != 5;  // ablation modes without the stream
+  constexpr bool kDma = MODE != 4 && MODE != 5;  // decomposition arms without the stream
   constexpr bool kLists = MODE == 8;
   constexpr int PPW = S::PPW;
-  constexpr int kPD0 = (VAR & 64) ? 3 : ((VAR & 32) ? 2 : 1);
-  constexpr int kPD = ((S::CPT * S::CT) % (kPD0 + 1) == 0) ? kPD0 : 1;
   // each step's fragment reads + MFMAs kept in program order, so the one-step
   // prefetch survives scheduling (3.38 vs 3.63 ms at 10M rows); the sorted-list
   // pass would spill with it
-  constexpr bool kPin = (VAR & 128) != 0 || MODE != 8;
-  // VAR 4194304 (ablation, r03): instead of pinning a step's fragment reads
-  // ahead of its MFMAs, ask the scheduler to interleave them: after every G
-  // MFMAs one ds_read_b128 of a later step (sched_group_barrier), so the LDS
-  // reads issue in the MFMA gaps rather than in one burst
-  constexpr bool kIlvSched = (VAR & 4194304) != 0;
-  // VAR 8192 (ablation): per-workgroup start / end wall clock into a.lists
+  constexpr bool kPin = MODE != 8;
+  // VAR 8192 (tools): per-workgroup start / end wall clock into a.lists
   constexpr bool kClock = (VAR & 8192) != 0;
   uint64_t tclk0 = 0;
   if constexpr (kClock) tclk0 = wall_clock64();
@@ -1975,7 +1953,11 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
   // is a scalar base advanced chunk by chunk (the chunk issued at step c is
   // c + AHEAD). Tiles past the last row read the collection's 32 rows of
   // allocation padding (vs_engine.cpp grow()) and are masked in the epilogue.
-  constexpr bool kNtDma = (MODE == 0) != ((VAR & 1024) != 0);
+  // The main pass streams the corpus non-temporally (with its register
+  // counters: -2.0% at 1.25M rows and -1.2% at 10M against LDS counters and
+  // default-policy DMA, r01, 2 x 40 / 16 reps); the other modes use the
+  // default load policy.
+  constexpr bool kNtDma = MODE == 0;
   const uint32_t lds_base = (uint32_t)(uintptr_t)(lds_ptr_t)smem;
   uint32_t loff[PPW];
 #pragma unroll
@@ -1985,18 +1967,9 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
     const int g_ri = lane >> 3, c16 = (lane & 7) ^ mf_swz(g_ri, rg);
     loff[i] = (uint32_t)((rg * 8 + g_ri) * RBY + s4l * 128 + c16 * 16);
   }
-  constexpr bool kSpread = (VAR & 512) != 0;  // pieces spread over the chunk's steps
   const unsigned char* xnext = (const unsigned char*)a.X + (size_t)wr0 * RBY;  // next chunk to issue
   uint32_t unext = 0;     // its chunk index within the tile
   uint32_t snext = 0;     // its ring slot byte offset
-  auto issue_piece = [&](int i) {
-    const int b = w + WAVES * i;
-    const int s4l = b >> 2, rg = b & 3;
-    if constexpr (MODE == 11)
-      glds4(xnext, loff[i], lds_base + snext + (uint32_t)((s4l * 4 + rg) * 1024));
-    else
-      glds16<kNtDma>(xnext, loff[i], lds_base + snext + (uint32_t)((s4l * 4 + rg) * 1024));
-  };
   auto advance = [&]() {
     const bool last = unext == S::CPT - 1;
     xnext += last ? (size_t)(32 * RBY - (S::CPT - 1) * S::CS4 * 128) : (size_t)S::CS4 * 128;
@@ -2004,99 +1977,55 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
     snext = snext + S::CHUNK_BYTES == (uint32_t)(S::NSLOT * S::CHUNK_BYTES) ? 0
                                                                            : snext + S::CHUNK_BYTES;
   };
-  auto issue_next = [&]() {
-#pragma unroll
-    for (int i = 0; i < PPW; ++i) issue_piece(i);
-    advance();
-  };
-  // Branch-free stream (default of the product passes, MODE 0 / 3 / 8; VAR
-  // 524288 flips it: back to the conditional stream, or on for ablation
-  // modes; r02: main pass -2.5 to -3.2% at 10M / 1.25M rows, back to back).
-  // Every chunk step issues its pieces: past
-  // the last chunk they re-read the workgroup's first chunk (valid memory, an
-  // L2 hit) into the slot being refilled, which is never read again; so the
-  // vmcnt waits are the same every step (no branches in the chunk loop, which
-  // let hipcc's waitcnt pass keep the fragment reads' order: lgkmcnt(2), not
-  // lgkmcnt(0), before a chunk's first MFMAs). Drained before the exit.
-  constexpr bool kBF = (((VAR & 524288) != 0) != (MODE == 0 || MODE == 3 || MODE == 8)) && !kSpread;
+  // Branch-free stream (r02: main pass -2.5 to -3.2% at 10M / 1.25M rows
+  // against a stream that issued only real chunks, back to back). Every chunk
+  // step issues its pieces: past the last chunk they read valid memory into
+  // the slot being refilled, which is never read again; so the vmcnt waits
+  // are the same every step (no branches in the chunk loop, which let hipcc's
+  // waitcnt pass keep the fragment reads' order: lgkmcnt(2), not lgkmcnt(0),
+  // before a chunk's first MFMAs). Drained before the exit.
   // The dummy pieces past the last chunk all read the pass's FIRST chunk (the
   // same bytes for every workgroup: L2 hits after one miss per XCD). r05: each
   // workgroup re-read its own first chunk, which the stream had long evicted:
   // AHEAD x 24 KiB x 256 workgroups of HBM re-reads, +2.2% of the traffic at
   // the N = 8 share (profiles/pmc_traffic.json c3_i8@1250000, build 67398432).
   const unsigned char* const xsafe = (const unsigned char*)a.X;
-  auto bf_src = [&](bool real) -> const unsigned char* {
+  auto issue_next = [&](bool real) {  // this wave's pieces of the next chunk, or the dummy
     // wave-uniform by construction; readfirstlane keeps it in SGPRs for the
     // asm's "s" operand whatever the divergence analysis concludes
     const uint64_t sp = (uint64_t)(uintptr_t)(real ? xnext : xsafe);
-    return (const unsigned char*)(uintptr_t)(
+    const unsigned char* src = (const unsigned char*)(uintptr_t)(
         ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(sp >> 32)) << 32) |
         (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)sp));
-  };
-  auto bf_piece = [&](const unsigned char* src, int i) {
-    const int b = w + WAVES * i;
-    const int s4l = b >> 2, rg = b & 3;
-    glds16<kNtDma>(src, loff[i],
-                   (uint32_t)__builtin_amdgcn_readfirstlane(
-                       (int)(lds_base + snext + (uint32_t)((s4l * 4 + rg) * 1024))));
-  };
-  auto issue_next_bf = [&](bool real) {
-    const unsigned char* src = bf_src(real);
 #pragma unroll
-    for (int i = 0; i < PPW; ++i) bf_piece(src, i);
+    for (int i = 0; i < PPW; ++i) {
+      const int b = w + WAVES * i;
+      const int s4l = b >> 2, rg = b & 3;
+      glds16<kNtDma>(src, loff[i],
+                     (uint32_t)__builtin_amdgcn_readfirstlane(
+                         (int)(lds_base + snext + (uint32_t)((s4l * 4 + rg) * 1024))));
+    }
     advance();
   };
-  // VAR 8388608 (r04): the ring's first AHEAD chunks are issued before the
-  // query-fragment prologue instead of after it, so the corpus fill (~5 us at
-  // ~25 GB/s per CU) overlaps the ~6 us of B-fragment loads from L2 that every
-  // launch starts with; the prologue's vmcnt(0) drain then covers both.
-  constexpr bool kEarlyFill = (VAR & 8388608) != 0;
-  // VAR 33554432 (r05, int8 pass): one barrier per PAIR of chunks (tiles: a
-  // 24 KiB chunk is one 32-row tile of 768-B int8 rows) instead of one per
-  // chunk, and the two freed slots refilled at once. With 6 slots: before the
-  // barrier of the pair (c, c + 1) chunks up to c + 2 have landed (c + 3 may
-  // pend), the barrier frees the previous pair's slots, and chunks c + 4,
-  // c + 5 are issued into them (4 chunks ahead instead of 5). The per-tile
-  // fixed cost (wait, barrier, DMA issue) is half the int8 pass's 48 MFMAs
-  // per wave and tile where the bf16 pass had 96.
-  constexpr bool kPair = (VAR & 33554432) != 0 && kBF && S::CPT == 1 && S::NSLOT == 6 &&
-                         (VAR & 1048576) == 0 && kDma;
-  constexpr uint32_t kFill = kPair ? (uint32_t)S::AHEAD - 1 : (uint32_t)S::AHEAD;
-  // VAR 16384 (r05, ablation): the branch-free stream's pieces of a chunk
-  // spread over its steps -- piece 0 after the barrier, piece i after step
-  // i * CT / PPW -- instead of all PPW back to back after the barrier, where
-  // both waves of a SIMD issue theirs while the matrix pipe waits. Same
-  // slots and waits: every piece of chunk c + AHEAD is issued before the
-  // next chunk's vmcnt wait counts them.
-  constexpr bool kBFSpread = (VAR & 16384) != 0 && kBF && !kPair && (VAR & 1048576) == 0 && kDma &&
-                             PPW > 1 && S::CT >= PPW;
-  const unsigned char* bf_cur = xsafe;  // (kBFSpread) the chunk being issued
-  if constexpr (kDma && kBF && kEarlyFill) {
-#pragma unroll
-    for (uint32_t c = 0; c < kFill; ++c) issue_next_bf(c < nchunks);
-  }
   // B operand of group g: Q[query 32w+16g+col][32t + 8kq + j], j = 0..7.
   bf16x8_t qf[G][S::T];
   uint32_t ql[G];
   bool qvalid[G];
   float th_s[G];     // admit rows whose score reaches th_s
   int th_i[G];       // I8: admit rows whose int8 dot reaches th_i
-  // cntl[g * THREADS + tid]: keys this lane appended to its quarter of the
-  // query's buffer (candidate passes). The main pass keeps the counts and
-  // each lane's first slot in registers instead (no LDS round trip and no
-  // address rebuild in the append path; 256 VGPRs, no spill), and streams the
-  // corpus non-temporally: back to back, -2.0% at 1.25M rows and -1.2% at 10M
-  // against LDS counters and default-policy DMA (r01, 2 x 40 / 16 reps).
-  constexpr bool kRegCnt = MODE == 0 && (VAR & 131072) == 0;
+  // The main pass keeps the count of slabs this lane appended to its quarter
+  // of the query's buffer, and the quarter's first slot, in registers (no LDS
+  // round trip and no address rebuild in the append path; 256 VGPRs, no
+  // spill: see kNtDma for the measurement against counters in LDS).
+  constexpr bool kRegCnt = MODE == 0;
   uint32_t cnt_r[G], slot0[G];
   int qmx_r[G];  // I8: the largest dot this lane appended (INT_MIN: none)
 #pragma unroll
   for (int g = 0; g < G; ++g) {
     qmx_r[g] = INT_MIN;
-    // (the register-count main pass keeps each lane's running quarter maximum
-    // here instead: score_ord of the largest admitted score, 0 = none)
+    // cntl[g * THREADS + tid]: this lane's running quarter maximum,
+    // score_ord of the largest admitted score, 0 = none
     if constexpr (kCntBytes > 0) cntl[g * THREADS + threadIdx.x] = 0u;
-    if constexpr (kLdsCnt) cntl[(G + g) * THREADS + threadIdx.x] = 0u;
     if constexpr (kRegCnt) {
       cnt_r[g] = 0u;
       slot0[g] = (uint32_t)(((size_t)blockIdx.x * kMfmaQueries +
@@ -2112,7 +2041,7 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
     if constexpr (I8) th_i[g] = q8_dot_threshold(a, ql[g], qvalid[g], th_s[g]);
   }
 
-  // VAR 8192: the prologue's loads drained and timed (ablation only)
+  // VAR 8192: the prologue's loads drained and timed (tools only)
   uint64_t tclk1 = 0, tclk2 = 0;
   if constexpr (kClock) {
     __builtin_amdgcn_s_waitcnt(0);
@@ -2137,41 +2066,25 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
   // does not place vmcnt waits for them inside the loop, where the hardware
   // counter also holds the ring's LDS-DMA pieces (invisible to the pass).
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), expcnt/lgkmcnt untouched
-  if constexpr (MODE == 12) {  // ablation: the prologue's query-fragment loads only
-#pragma unroll
-    for (int g = 0; g < G; ++g) asm volatile("" ::"v"(qf[g][0]), "v"(qf[g][S::T - 1]));
-    return;
-  }
   __syncthreads();  // lists / counts initialised
-  if constexpr (kDma && kBF) {
-    if constexpr (!kEarlyFill) {
+  if constexpr (kDma) {  // fill the ring and publish chunk 0
 #pragma unroll
-      for (uint32_t c = 0; c < kFill; ++c) issue_next_bf(c < nchunks);
-    }
-    wait_vmcnt<PPW * (kFill - 1)>();
-  } else {
-    if constexpr (kDma)
-      for (uint32_t c = 0; c < (uint32_t)S::AHEAD; ++c)
-        if (c < nchunks) issue_next();
-    // publish chunk 0
-    if ((uint32_t)S::AHEAD <= nchunks)
-      wait_vmcnt<PPW * (S::AHEAD - 1)>();
-    else
-      wait_vmcnt<0>();
+    for (uint32_t c = 0; c < (uint32_t)S::AHEAD; ++c) issue_next(c < nchunks);
+    wait_vmcnt<PPW * (S::AHEAD - 1)>();
   }
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
 
-  // A fragments are read PD 32-k steps ahead of their MFMAs, across chunk
+  // A fragments are read one 64-B step ahead of their MFMAs, across chunk
   // boundaries inside a tile: chunk c+1 is published by the barrier at the
-  // head of chunk c, so the reads for the first PD steps of chunk c+1 are
-  // issued during the last steps of chunk c. A tile's first PD steps are
-  // read after the previous tile's epilogue, before the first barrier (its
-  // chunk was published one barrier earlier), so no fragment is live across
-  // the epilogue. NB = PD + 1 register sets rotate with the step index,
-  // which repeats every tile because NB divides the steps per tile.
+  // head of chunk c, so the read for the first step of chunk c+1 is issued
+  // during the last step of chunk c. A tile's first step is read after the
+  // previous tile's epilogue, before the first barrier (its chunk was
+  // published one barrier earlier), so no fragment is live across the
+  // epilogue. NB = 2 register sets alternate with the step index, which
+  // repeats every tile because the steps per tile are even.
   constexpr int STEPS = S::CPT * S::CT;
-  constexpr int NB = kPD + 1;
+  constexpr int NB = 2;
   static_assert(STEPS % NB == 0, "A-fragment ring must divide the steps per tile");
   uint32_t scur = 0;  // ring slot byte offset of chunk c
   // Candidate passes instantiate a tile's body twice: full 32-row tiles get a
@@ -2179,35 +2092,15 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
   // The sorted-list pass keeps one body with a runtime test (its register
   // allocation with the peeled form spilled; r01).
   constexpr bool kPeel = MODE != 8;
-  // VAR 1048576 (with the branch-free stream): waves 4-7 run half a chunk
-  // ahead of their SIMD partners 0-3. Their per-chunk wait + barrier + DMA
-  // issue sits between steps CT/2 - 1 and CT/2 of the chunk instead of before
-  // step 0 (same barrier count, same slots: a wave only reads chunks the
-  // barrier before its steps published, and the slot refilled at barrier c,
-  // chunk c - 1's, is done for every wave), so the two waves of a SIMD reach
-  // their LDS-read bursts and barriers half a chunk apart instead of in
-  // lockstep (MI355X_MICROARCH.md, two waves per SIMD, item 9).
-  constexpr bool kStag = (VAR & 1048576) != 0 && kBF && WAVES == 8;
   // int8 pass epilogue of one tile (accumulators ac, first row trow0): a lane
   // whose largest dot of the tile reaches the query's integer threshold
   // appends its 8 dots (int32 bits) -- the select bounds and rescores them.
   // Padding and filtered-out rows (the pre-mask) are INT_MIN in the slab:
   // never a maximum, never a survivor.
-  // (r05) split in two halves, so the deferred form below can place them in
-  // different MFMA steps: q8_epi_mx masks query group g's dots of the tile
-  // (padding / filtered rows -> INT_MIN, in ac) and returns their maximum;
-  // q8_epi_app appends them when that reaches the group's threshold.
-  auto q8_epi_am = [&](uint32_t trow0) -> uint32_t {
-    uint32_t am = 0xFFu;
-    if (a.allow) {
-      const uint32_t tw = (uint32_t)(a.allow[trow0 >> 6] >> (trow0 & 32)) >> (4 * kq);
-      am = (tw & 0xFu) | ((tw >> 12) & 0xF0u);
-    }
-    return am;
-  };
-  // (may_filter false: the caller knows a.allow is null -- the split form)
-  auto q8_epi_mx = [&](f32x4_t (&ac)[2][G], int g, uint32_t trow0, bool full, uint32_t am,
-                       bool may_filter = true) -> int {
+  // q8_epi_mx masks query group g's dots of the tile (padding / filtered rows
+  // -> INT_MIN, in ac) and returns their maximum; q8_epi_app appends them
+  // when that reaches the group's threshold.
+  auto q8_epi_mx = [&](f32x4_t (&ac)[2][G], int g, uint32_t trow0, bool full, uint32_t am) -> int {
     // whole-vector bit casts: this hipcc miscompiles __builtin_bit_cast of
     // one ext_vector element (it reads element 0; tools/q8_check.hip found it)
     const i32x4_t a0 = __builtin_bit_cast(i32x4_t, ac[0][g]);
@@ -2215,7 +2108,7 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
     int v[8];
 #pragma unroll
     for (int b = 0; b < 4; ++b) v[b] = a0[b], v[4 + b] = a1[b];
-    if (!full || (may_filter && a.allow)) {  // uniform: unfiltered full tiles skip it
+    if (!full || a.allow) {  // uniform: unfiltered full tiles skip it
       // the row base and mask bits are taken opaque inside the branch: the
       // compiler otherwise hoists their 16 adds/ands into every unfiltered
       // full tile (r05 ISA: 17 of the epilogue's 38 VALU per tile)
@@ -2230,7 +2123,7 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
     return imax3(imax3(v[0], v[1], v[2]), imax3(v[3], v[4], v[5]), imax3(v[6], v[7], INT_MIN));
   };
   auto q8_epi_app = [&](f32x4_t (&ac)[2][G], int g, uint32_t trow0, int mx) {
-    // VAR 16777216 (timing ablation only, wrong answers): never append
+    // VAR 16777216 (tools' timing arm only, wrong answers): never append
     if ((VAR & 16777216) != 0) {
       asm volatile("" ::"v"(mx >= th_i[g]));
       return;
@@ -2253,62 +2146,28 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
     }
   };
   auto q8_epi = [&](f32x4_t (&ac)[2][G], uint32_t trow0, bool full) {
-    const uint32_t am = q8_epi_am(trow0);
+    uint32_t am = 0xFFu;
+    if (a.allow) {
+      const uint32_t tw = (uint32_t)(a.allow[trow0 >> 6] >> (trow0 & 32)) >> (4 * kq);
+      am = (tw & 0xFu) | ((tw >> 12) & 0xF0u);
+    }
 #pragma unroll
     for (int g = 0; g < G; ++g) q8_epi_app(ac, g, trow0, q8_epi_mx(ac, g, trow0, full, am));
   };
-  // VAR 67108864 (r05, int8 pass): the epilogue of tile t runs after the first
-  // step's MFMAs of tile t + 1, on the other of two accumulator sets, so its
-  // VALU work and its wait for the tile's last MFMA results overlap the
-  // matrix pipe instead of stalling it at every tile's end
-  constexpr bool kEpiPipe = I8 && MODE == 0 && (VAR & 67108864) != 0;
-  f32x4_t accq[kEpiPipe ? 2 : 1][2][G];
-  uint32_t prow0 = 0;
-  bool pfull = true, have_prev = false;
-  // VAR 65536 (r05, with 67108864): the deferred epilogue split over the next
-  // tile's steps -- group g's maximum after step 1 + g, the appends after
-  // step G + 1 -- so its compares sit in the MFMA steps' issue gaps instead
-  // of one block. Only full tiles are deferred (a partial last tile runs its
-  // own at once); the first tile's "previous" set starts as INT_MIN dots,
-  // which never pass, so no step tests whether a previous tile exists.
-  constexpr bool kEpiSplit = kEpiPipe && (VAR & 65536) != 0;
-  // (the launcher runs this form only without a filter: a.allow is null)
-  int mxp[G];
-  if constexpr (kEpiSplit) {
-#pragma unroll
-    for (int hr = 0; hr < 2; ++hr)
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        accq[1][hr][g] = __builtin_bit_cast(f32x4_t, i32x4_t{INT_MIN, INT_MIN, INT_MIN, INT_MIN});
-        mxp[g] = INT_MIN;
-      }
-    prow0 = wr0;
-  }
-  // VAR 32768 (r05, ablation): a tile's first PD A-fragment reads are issued
-  // at the end of the previous tile, before its epilogue (the next tile's
-  // first chunk was published by the barrier at the head of this tile's last
-  // chunk), so their LDS latency overlaps the epilogue instead of opening
-  // the next tile after its barrier
-  constexpr bool kPreA = (VAR & 32768) != 0 && MODE != 2 && MODE != 7 && !kStag;
-  constexpr int kAH = MODE == 10 || MODE == 13 ? 1 : 2;
-  bf16x8_t afr_k[NB][2];
-  auto read_first = [&]() {
-#pragma unroll
-    for (int p = 0; p < kPD; ++p)
-#pragma unroll
-      for (int hr = 0; hr < kAH; ++hr) afr_k[p][hr] = lds_a(smem + scur, p, hr);
-  };
-  auto tile = [&](uint32_t t, auto full_tag, auto stag_tag, auto set_tag) {
-    constexpr bool STAG = decltype(stag_tag)::value;
-    constexpr int SET = decltype(set_tag)::value;
-    constexpr int SYNC_STEP = STAG ? S::CT / 2 : 0;
-    f32x4_t (&acc)[2][G] = accq[kEpiPipe ? SET : 0];  // [row half][query group]
+  // The one accumulator set lives out here and a tile binds it by reference;
+  // the tile loops below stay in lambdas of their own (run_tiles over tile_p
+  // over tile). Neither is free to change: hipcc optimises each lambda before
+  // it inlines it, and with the set local to the tile, or the loops written
+  // straight into the kernel, every pass comes out with other code
+  // (compared by assembly).
+  f32x4_t acc_set[2][G];
+  auto tile = [&](uint32_t t, auto full_tag) {
+    f32x4_t (&acc)[2][G] = acc_set;  // [row half][query group]
 #pragma unroll
     for (int hr = 0; hr < 2; ++hr)
 #pragma unroll
       for (int g = 0; g < G; ++g) acc[hr][g] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    bf16x8_t afr_l[NB][2];
-    bf16x8_t(&afr)[NB][2] = *(kPreA ? &afr_k : &afr_l);
+    bf16x8_t afr[NB][2];
 #pragma unroll
     for (int u = 0; u < S::CPT; ++u) {
       const uint32_t c = t * S::CPT + u;
@@ -2316,65 +2175,28 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
           scur + S::CHUNK_BYTES == (uint32_t)(S::NSLOT * S::CHUNK_BYTES) ? 0 : scur + S::CHUNK_BYTES;
       const unsigned char* sb = smem + scur;
       const unsigned char* sbn = smem + snxt;
-      if (MODE != 2 && u == 0 && !kPreA) {
+      if (MODE != 2 && u == 0) {
 #pragma unroll
-        for (int p = 0; p < kPD; ++p)
-#pragma unroll
-          for (int hr = 0; hr < (MODE == 10 || MODE == 13 ? 1 : 2); ++hr) afr[p][hr] = lds_a(sb, p, hr);
+        for (int hr = 0; hr < 2; ++hr) afr[0][hr] = lds_a(sb, 0, hr);
       }
-      const bool refill = kDma && c + S::AHEAD < nchunks;
-      auto sync_chunk = [&]() {
-        __builtin_amdgcn_sched_barrier(0);
-        // chunk c+1 landed for this wave: chunks c+2 .. c+AHEAD-1 may pend
-        // (pairs: chunks up to c+2 landed, c+3 may pend)
-        if constexpr (kPair) {
-          wait_vmcnt<PPW>();
-        } else if constexpr (kDma && kBF) {
-          wait_vmcnt<PPW * (S::AHEAD - 2)>();
-        } else if constexpr (kDma) {
-          if (c + S::AHEAD <= nchunks)
-            wait_vmcnt<PPW * (S::AHEAD - 2)>();
-          else
-            wait_vmcnt<0>();
-        }
-        // VAR 134217728 (timing ablation only: the ring is then unsynchronised
-        // and the results garbage): no barrier at all
-        if constexpr (MODE != 5 && (VAR & 134217728) == 0)
-          __builtin_amdgcn_s_barrier();  // chunk c+1 visible; slot c-1 free
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (kPair) {
-          issue_next_bf(c + 4 < nchunks);
-          issue_next_bf(c + 5 < nchunks);
-        } else if constexpr (kBFSpread) {
-          bf_cur = bf_src(refill);
-          bf_piece(bf_cur, 0);
-        } else if constexpr (kDma && kBF) {
-          issue_next_bf(refill);
-        } else if (!kSpread && refill) {
-          issue_next();
-        }
-      };
-      if constexpr (kPair) {
-        if ((c & 1u) == 0) sync_chunk();  // uniform
-      } else if constexpr (!STAG || MODE == 2) {
-        sync_chunk();
-      }
+      const bool refill = kDma && c + S::AHEAD < nchunks;  // else the dummy
+      __builtin_amdgcn_sched_barrier(0);
+      // chunk c+1 landed for this wave: chunks c+2 .. c+AHEAD-1 may pend
+      if constexpr (kDma) wait_vmcnt<PPW * (S::AHEAD - 2)>();
+      if constexpr (MODE != 5) __builtin_amdgcn_s_barrier();  // chunk c+1 visible; slot c-1 free
+      __builtin_amdgcn_sched_barrier(0);
+      if constexpr (kDma) issue_next(refill);
       if constexpr (MODE != 2) {
 #pragma unroll
         for (int s = 0; s < S::CT; ++s) {
-          if constexpr (STAG) {
-            if (s == SYNC_STEP) sync_chunk();
-          }
           const int sig = u * S::CT + s;
-          // prefetch step sig + PD (this chunk or the next one)
-          if (MODE != 7 && sig + kPD < STEPS) {
-            const int sp = s + kPD;
+          // prefetch step sig + 1 (this chunk or the next one)
+          if (sig + 1 < STEPS) {
 #pragma unroll
-            for (int hr = 0; hr < (MODE == 10 || MODE == 13 ? 1 : 2); ++hr)
-              afr[(sig + kPD) % NB][hr] =
-                  sp < S::CT ? lds_a(sb, sp, hr) : lds_a(sbn, sp - S::CT, hr);
+            for (int hr = 0; hr < 2; ++hr)
+              afr[(sig + 1) % NB][hr] = s + 1 < S::CT ? lds_a(sb, s + 1, hr) : lds_a(sbn, 0, hr);
           }
-          if constexpr (kPin && !kIlvSched) __builtin_amdgcn_sched_barrier(0);
+          if constexpr (kPin) __builtin_amdgcn_sched_barrier(0);
           if constexpr (F32) {
             // lane (col, kq) holds k = 16 step + 4 kq + j in element j of both
             // fragments: MFMA j sums those k over the four lane quarters
@@ -2393,72 +2215,27 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
           } else {
 #pragma unroll
             for (int hr = 0; hr < 2; ++hr) {
-              const bf16x8_t av = afr[MODE == 7 ? 0 : sig % NB][MODE == 10 || MODE == 13 ? 0 : hr];
+              const bf16x8_t av = afr[sig % NB][hr];
 #pragma unroll
               for (int g = 0; g < G; ++g) {
-                // MODE 13 (ablation): half the A reads with every MFMA kept --
-                // row half 1 reuses half 0's fragment against the next step's
-                // query fragment (a distinct chain, so nothing merges)
-                const int qs = MODE == 13 && hr == 1 ? (sig + 1) % S::T : sig;
                 if constexpr (I8)  // 64 int8 k per step; exact int32 sums (bits kept in acc)
                   acc[hr][g] = __builtin_bit_cast(
                       f32x4_t, __builtin_amdgcn_mfma_i32_16x16x64_i8(
                                    __builtin_bit_cast(i32x4_t, av),
-                                   __builtin_bit_cast(i32x4_t, qf[g][qs]),
+                                   __builtin_bit_cast(i32x4_t, qf[g][sig]),
                                    __builtin_bit_cast(i32x4_t, acc[hr][g]), 0, 0, 0));
                 else
-                  acc[hr][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, qf[g][qs], acc[hr][g], 0,
+                  acc[hr][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, qf[g][sig], acc[hr][g], 0,
                                                                        0, 0);
               }
             }
           }
-          if constexpr (kIlvSched) {
-#pragma unroll
-            for (int hr = 0; hr < 2; ++hr) {
-              __builtin_amdgcn_sched_group_barrier(0x008, G, 0);  // G MFMAs
-              __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // one DS read
-            }
-          }
           if constexpr (kPin) __builtin_amdgcn_sched_barrier(0);
-          if constexpr (kEpiSplit) {
-            if (u == 0) {  // compile-time: u, s unrolled
-              if (s >= 1 && s <= G)
-                mxp[s - 1] = q8_epi_mx(accq[1 - SET], s - 1, prow0, true, 0xFFu, false);
-              if (s == G + 1) {
-#pragma unroll
-                for (int g = 0; g < G; ++g) q8_epi_app(accq[1 - SET], g, prow0, mxp[g]);
-              }
-            }
-          } else if constexpr (kEpiPipe) {
-            if (u == 0 && s == 0 && have_prev) {
-              q8_epi(accq[1 - SET], prow0, pfull);
-              __builtin_amdgcn_sched_barrier(0);
-            }
-          }
-          if constexpr (kBFSpread) {
-#pragma unroll
-            for (int i = 1; i < PPW; ++i)
-              if (s == (i * S::CT) / PPW) {
-                bf_piece(bf_cur, i);
-                if (i == PPW - 1) advance();
-              }
-          }
-          if constexpr (kSpread) {
-            // piece i after step i * CT / PPW (the last one also advances)
-#pragma unroll
-            for (int i = 0; i < PPW; ++i)
-              if (s == (i * S::CT) / PPW && refill) {
-                issue_piece(i);
-                if (i == PPW - 1) advance();
-              }
-          }
         }
       }
       scur = snxt;
     }
-    if constexpr (kPreA) read_first();  // the next tile's (past the last: unused)
-    if constexpr (MODE == 1 || MODE == 2 || MODE == 4 || MODE == 5 || MODE == 7 || MODE == 10 ||
-                  MODE == 11 || MODE == 13) {
+    if constexpr (MODE == 1 || MODE == 2 || MODE == 4 || MODE == 5) {  // no epilogue
 #pragma unroll
       for (int hr = 0; hr < 2; ++hr)
 #pragma unroll
@@ -2489,16 +2266,7 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
       }
     }
     if constexpr (I8 && MODE == 0) {
-      if constexpr (kEpiSplit) {  // full tiles: in the next tile's steps (or at the end)
-        if (full)
-          prow0 = trow0;
-        else
-          q8_epi(acc, trow0, false);
-      } else if constexpr (kEpiPipe) {  // run after the next tile's first step (or at the end)
-        prow0 = trow0, pfull = full, have_prev = true;
-      } else {
-        q8_epi(acc, trow0, full);
-      }
+      q8_epi(acc, trow0, full);
       return;
     } else if constexpr (I8) {
 #pragma unroll
@@ -2543,26 +2311,23 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
         // seven at the next chunk barrier (r01: -0.12 ms at 1.25M rows).
         if (qvalid[g] && mx >= th_s[g] && mx != -INFINITY) {
           const uint32_t sub = a.cand_cap >> 2;
-          const uint32_t cg = kRegCnt ? cnt_r[g] : cntl[g * THREADS + threadIdx.x];
+          const uint32_t cg = cnt_r[g];
           if (cg >= sub) {
-            // VAR 131072 (LDS counters, ablation only) drops the slab: inexact
             // The quarter is full (many near-equal rows): keep the sub slabs
             // with the largest maximum keys. A slab this evicts (or never
             // stores) has a maximum key below those of all sub slabs kept,
             // i.e. below sub >= k keys of distinct rows, so none of its rows
             // can be in the top k (mfma_cand_cap gives sub >= k): exact, with
             // no re-run. Rare path: the slabs are read back from memory.
-            // VAR 2097152 (ablation): drops the slab, inexact
-            if constexpr (kRegCnt && (VAR & 2097152) == 0) {
-              mf_replace_min(a, slot0[g], sub, acc[0][g], acc[1][g], a.row_base + trow0, mx);
-              // the quarter's maximum never leaves it (a replacement evicts the
-              // smallest), so the running maximum stays exact
-              mf_quarter_max(cntl, g * THREADS, mx);
-            }
-          } else if constexpr (kRegCnt) {
-            // VAR 262144 (ablation): the appending wave runs at raised
-            // priority, so it reaches the next chunk barrier sooner
-            if constexpr ((VAR & 262144) != 0) __builtin_amdgcn_s_setprio(3);
+            mf_replace_min(a, slot0[g], sub, acc[0][g], acc[1][g], a.row_base + trow0, mx);
+            // the quarter's maximum never leaves it (a replacement evicts the
+            // smallest), so the running maximum stays exact
+            mf_quarter_max(cntl, g * THREADS, mx);
+          } else {
+            // slot layout [wg][query][cap], a quarter = sub slots: a
+            // workgroup's stores stay in its own region (a query-major layout
+            // spread each wave's stores over 16 regions 0.5 MiB apart: +4%
+            // main pass, r01)
             const size_t slot = (size_t)slot0[g] + cg;
             f32x4_t* sp = (f32x4_t*)a.cand + 2 * slot;
             sp[0] = acc[0][g];
@@ -2570,24 +2335,6 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
             a.cand_tile[slot] = a.row_base + trow0;
             cnt_r[g] = cg + 1;
             mf_quarter_max(cntl, g * THREADS, mx);
-            if constexpr ((VAR & 262144) != 0) __builtin_amdgcn_s_setprio(0);
-          } else {
-            // the address is rebuilt here from an opaque thread id, so none
-            // of it is hoisted out of the tile loop (its register budget)
-            uint32_t tid = threadIdx.x;
-            asm volatile("" : "+v"(tid));
-            // layout [wg][query][cap], a quarter = sub slots: a workgroup's
-            // stores stay in its own region (a query-major layout spread each
-            // wave's stores over 16 regions 0.5 MiB apart: +4% main pass, r01)
-            const uint32_t qo = (tid >> 6) * QPW + g * 16 + (tid & 15);
-            const size_t slot = ((size_t)blockIdx.x * kMfmaQueries + qo) * a.cand_cap +
-                                ((tid & 63) >> 4) * sub + cg;
-            f32x4_t* sp = (f32x4_t*)a.cand + 2 * slot;
-            sp[0] = acc[0][g];
-            sp[1] = acc[1][g];
-            a.cand_tile[slot] = a.row_base + trow0;
-            cntl[g * THREADS + threadIdx.x] = cg + 1;
-            mf_quarter_max(cntl, (G + g) * THREADS, mx);
           }
         }
         continue;
@@ -2628,52 +2375,19 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
       }
     }
   };
-  if constexpr (kPreA) read_first();  // tile 0's (chunk 0 published above)
   uint32_t nfull = (wr1 - wr0) / 32;
   if (nfull > ntiles) nfull = ntiles;
-  // (kEpiPipe) tiles alternate between the two accumulator sets
-  auto tile_p = [&](uint32_t t, auto full_tag, auto stag_tag) {
-    if constexpr (kEpiPipe) {
-      if (t & 1u)
-        tile(t, full_tag, stag_tag, MfSet<1>{});
-      else
-        tile(t, full_tag, stag_tag, MfSet<0>{});
-    } else {
-      tile(t, full_tag, stag_tag, MfSet<0>{});
-    }
-  };
-  auto run_tiles = [&](auto stag_tag) {
+  auto tile_p = [&](uint32_t t, auto full_tag) { tile(t, full_tag); };
+  auto run_tiles = [&]() {
     if constexpr (kPeel) {
-      for (uint32_t t = 0; t < nfull; ++t) tile_p(t, MfFull<true>{}, stag_tag);
-      for (uint32_t t = nfull; t < ntiles; ++t) tile_p(t, MfFull<false>{}, stag_tag);
+      for (uint32_t t = 0; t < nfull; ++t) tile_p(t, MfFull<true>{});
+      for (uint32_t t = nfull; t < ntiles; ++t) tile_p(t, MfFull<false>{});
     } else {
-      for (uint32_t t = 0; t < ntiles; ++t) tile_p(t, MfFull<false>{}, stag_tag);
-    }
-    if constexpr (kEpiSplit) {  // the last tile's, when it is a deferred full one
-      if (ntiles == nfull && nfull > 0) {
-        if ((nfull - 1) & 1u)
-          q8_epi(accq[1], prow0, true);
-        else
-          q8_epi(accq[0], prow0, true);
-      }
-    } else if constexpr (kEpiPipe) {  // the last tile's epilogue
-      if (have_prev) {
-        if ((ntiles - 1) & 1u)
-          q8_epi(accq[1], prow0, pfull);
-        else
-          q8_epi(accq[0], prow0, pfull);
-      }
+      for (uint32_t t = 0; t < ntiles; ++t) tile_p(t, MfFull<false>{});
     }
   };
-  if constexpr (kStag) {
-    if (w >= 4)
-      run_tiles(MfFull<true>{});
-    else
-      run_tiles(MfFull<false>{});
-  } else {
-    run_tiles(MfFull<false>{});
-  }
-  if constexpr (kDma && kBF) wait_vmcnt<0>();  // no LDS-DMA outlives the workgroup
+  run_tiles();
+  if constexpr (kDma) wait_vmcnt<0>();  // no LDS-DMA outlives the workgroup
   if constexpr (kClock) tclk2 = wall_clock64();
   // each wave owns its queries' lists / counters: no barrier before the write-out
 #pragma unroll
@@ -2683,11 +2397,8 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
       // r05: select_q8 reads a query's 4 nwg quarters in one coalesced load)
       const size_t ci = I8 ? ((size_t)ql[g] * gridDim.x + blockIdx.x) * 4 + kq
                            : ((size_t)blockIdx.x * kMfmaQueries + ql[g]) * 4 + kq;
-      a.cand_cnt[ci] = kRegCnt ? cnt_r[g] : cntl[g * THREADS + threadIdx.x];
-      if (a.cand_max)
-        a.cand_max[ci] =
-            kRegCnt ? (I8 ? (uint32_t)qmx_r[g] : cntl[g * THREADS + threadIdx.x])
-                    : cntl[(G + g) * THREADS + threadIdx.x];
+      a.cand_cnt[ci] = cnt_r[g];
+      if (a.cand_max) a.cand_max[ci] = I8 ? (uint32_t)qmx_r[g] : cntl[g * THREADS + threadIdx.x];
     } else if constexpr (MODE == 3) {
       // a workgroup with fewer tiles than max_tiles: the rest are empty
       for (uint32_t t = ntiles + kq; t < a.max_tiles; t += 4)
@@ -2856,12 +2567,6 @@ bool q8_supported(uint32_t dim, bool f32) {
   return f32 ? dim == 768 : (dim == 768 || dim == 1024);
 }
 
-template <int VAR>
-static hipError_t launch_q8_var(uint32_t nwg, const MfArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL((mfma_topk_kernel<768, 0, VAR, 2, false, true>), dim3(nwg), dim3(512), 0, st, a);
-  return hipGetLastError();
-}
-
 hipError_t launch_mfma_cand_q8(const void* X8, uint32_t dim, uint32_t n_rows, uint32_t row_base,
                                const void* Q8, uint32_t nq_valid, uint32_t k,
                                const float* init_score, const float* q8par, const float* q8glob,
@@ -2885,16 +2590,9 @@ hipError_t launch_mfma_cand_q8(const void* X8, uint32_t dim, uint32_t n_rows, ui
                        st, a);
     return hipGetLastError();
   }
-  static const int var = [] {
-    const char* e = getenv("VS_Q8_VAR");
-    return e ? atoi(e) : 2048 + 256;
-  }();
-  switch (var) {  // VS_Q8_VAR: ablation arms (read once)
-    case 0: return launch_q8_var<0>(*nlists, a, st);
-    case 256: return launch_q8_var<256>(*nlists, a, st);
-    case 2048 + 256 + 16777216: return launch_q8_var<2048 + 256 + 16777216>(*nlists, a, st);
-    default: return launch_q8_var<2048 + 256>(*nlists, a, st);
-  }
+  hipLaunchKernelGGL((mfma_topk_kernel<768, 0, 2048 + 256, 2, false, true>), dim3(*nlists), dim3(512),
+                     0, st, a);
+  return hipGetLastError();
 }
 
 uint32_t mfma_cand_cap(uint32_t n_rows, uint32_t k, uint32_t sample_tiles, double scale) {

@@ -27,15 +27,14 @@ struct Ctx {
   uint32_t* wgt;
   uint32_t nwg;
   hipEvent_t a, b;
-  float* tmax;  // sample-pass arms
-  uint32_t st;
+  bool weighted;  // run() takes the weighted split (wgt) instead of the even one
 };
 
 template <int MODE, int VAR, int G = 2>
 static float run(const Ctx& c, bool bound) {
   MfArgs a = c.args;
   if (!bound) a.init_score = nullptr;
-  if (VAR & 65536) a.wg_tile = c.wgt;  // ablation: the weighted split
+  if (c.weighted) a.wg_tile = c.wgt;
   // VS_ABL_BURST=B: B launches back to back per timing (sustained clocks, as
   // in a serving loop; the time per launch is returned). Default 1
   // (isolated launches). Isolated launches favoured a dynamic tile pool by
@@ -60,23 +59,12 @@ static float run_nq(const Ctx& c, bool bound) {
   return run<MODE, VAR, G>(c2, bound);
 }
 
-// the sample pass (MODE 3) over the first st tiles of every workgroup, same
-// burst rule as run(); its arguments are built from the main pass's
-template <int VAR>
-static float run_sample(const Ctx& c, bool) {
-  MfArgs a{};
-  a.X = c.args.X, a.Q = c.args.Q, a.tmax = c.tmax;
-  a.max_tiles = c.st, a.n_rows = c.args.n_rows, a.rows_per_wg = c.args.rows_per_wg;
-  a.nq_valid = 256, a.k = c.args.k;
-  static const int burst = getenv("VS_ABL_BURST") ? atoi(getenv("VS_ABL_BURST")) : 1;
-  hipEventRecord(c.a, 0);
-  for (int i = 0; i < burst; ++i)
-    hipLaunchKernelGGL((mfma_topk_kernel<768, 3, VAR, 2>), dim3(c.nwg), dim3(512), 0, 0, a);
-  hipEventRecord(c.b, 0);
-  hipEventSynchronize(c.b);
-  float ms = 0;
-  hipEventElapsedTime(&ms, c.a, c.b);
-  return ms / burst;
+// run() over the weighted split (VS_XCD_W)
+template <int MODE, int VAR, int G = 2>
+static float run_weighted(const Ctx& c, bool bound) {
+  Ctx c2 = c;
+  c2.weighted = true;
+  return run<MODE, VAR, G>(c2, bound);
 }
 
 struct Arm {
@@ -139,16 +127,14 @@ int main(int argc, char** argv) {
   g.n_rows = n, g.rows_per_wg = rpw, g.nq_valid = 256, g.k = k;
   c.a = a;
   c.b = b;
-  c.tmax = tmax;
-  c.st = st;
   // An unrolled, predicated candidate append was no faster than the ctz loop;
   // 4-16 sample tiles at 1.25M rows cut the candidates 2-8x but the main pass
   // gained what the sample pass lost (argv[3] overrides the sample tiles).
-  // 24 / 48 KiB K-chunks (VAR 2048 / 4096, + 256 for the 144 KiB ring) were
-  // slower than 16 KiB at 10M rows (3.64-3.67 vs 3.48 ms); kept as arms.
   // G = 4 (4 waves x 64 queries, one wave per SIMD, 512 registers): no
-  // epilogue 4.23 ms, 3.74 with a 2-step fragment prefetch, 3.60 with a pinned
-  // 3-step one, vs 3.35 for G = 2 (10M rows, r01).
+  // epilogue 4.23 ms vs 3.35 for G = 2 (10M rows, r01). The arms of
+  // experiments since taken out of the kernel (prefetch depths, 48 KiB
+  // chunks, staggered waves, ...): DESIGN.md, "Experiments removed from the
+  // MFMA scan".
   // weighted split: VS_XCD_W = 8 comma-separated weights for blockIdx % 8
   uint32_t* wgt = nullptr;
   {
@@ -179,53 +165,20 @@ int main(int argc, char** argv) {
   std::vector<Arm> arms = {
       {"main (product)", run<0, 2048 + 256, 2>, true, {}},  // 24 KiB chunks, 144 KiB ring
       {"main bf 16k", run<0, 0, 2>, true, {}},              // r02 build before: 16 KiB chunks
-      {"main branchy", run<0, 524288, 2>, true, {}},        // r01 conditional stream
-      {"bf no-replace", run<0, 2097152, 2>, true, {}},      // full quarter drops (inexact)
-      {"main bf stag", run<0, 1048576, 2>, true, {}},       // + waves 4-7 half a chunk ahead
       {"bf ring144", run<0, 256, 2>, true, {}},             // 8 chunks in flight
       {"bf 24k ring144", run<0, 2048 + 256, 2>, true, {}},  // 2 barriers / tile
-      {"bf 48k ring144", run<0, 4096 + 256, 2>, true, {}},  // 1 barrier / tile
-      {"main cached-dma", run<0, 1024, 2>, true, {}},       // regs, default policy
-      {"main lds-cnt", run<0, 131072, 2>, true, {}},        // LDS counters + nt
-      {"main v13", run<0, 131072 + 1024, 2>, true, {}},     // LDS counters, default policy
-      {"main prio", run<0, 262144, 2>, true, {}},           // default + raised priority appends
   };
-  // VS_ABL_SET=lds: what the A-fragment LDS reads cost (no epilogue in the
-  // MODE 1 / 7 / 10 arms: all reads, hr 0 only = half the reads, one
-  // fragment set reused = almost none)
   if (getenv("VS_ABL_SET") && !strcmp(getenv("VS_ABL_SET"), "g4")) {
     // one wave per SIMD, 64 queries each (half the A-fragment LDS reads), on
     // the product's 24 KiB chunks / 144 KiB ring, against the product layout
     arms = {{"no-epi (product)", run<1, 2048 + 256, 2>, false, {}},
-            {"no-epi G4 pd1", run<1, 2048 + 256, 4>, false, {}},
-            {"no-epi G4 pd3 pin", run<1, 2048 + 256 + 64 + 128, 4>, false, {}},
-            {"no-epi G4 pd2 pin", run<1, 2048 + 256 + 32 + 128, 4>, false, {}}};
-  } else if (getenv("VS_ABL_SET") && !strcmp(getenv("VS_ABL_SET"), "g4i")) {
-    // r03: the one-wave-per-SIMD 64-query layout with the step's fragment
-    // reads interleaved into its MFMAs by sched_group_barrier (VAR 4194304),
-    // against the product and the product interleaved the same way
-    arms = {{"main (product)", run<0, 2048 + 256, 2>, true, {}},
-            {"main ilv", run<0, 2048 + 256 + 4194304, 2>, true, {}},
-            {"main G4 ilv", run<0, 2048 + 256 + 4194304, 4>, true, {}},
-            {"no-epi (product)", run<1, 2048 + 256, 2>, false, {}},
-            {"no-epi ilv", run<1, 2048 + 256 + 4194304, 2>, false, {}},
-            {"no-epi G4 pd1", run<1, 2048 + 256, 4>, false, {}},
-            {"no-epi G4 ilv", run<1, 2048 + 256 + 4194304, 4>, false, {}},
-            {"no-epi G4 pd2 ilv", run<1, 2048 + 256 + 32 + 4194304, 4>, false, {}}};
-  } else if (getenv("VS_ABL_SET") && !strcmp(getenv("VS_ABL_SET"), "early")) {
-    // r04: the ring's first chunks issued before the query-fragment prologue
-    // (VAR 8388608) against the product order, main pass and sample pass
-    arms = {{"main (product)", run<0, 2048 + 256, 2>, true, {}},
-            {"main early", run<0, 2048 + 256 + 8388608, 2>, true, {}},
-            {"sample (product)", run_sample<2048 + 256>, false, {}},
-            {"sample early", run_sample<2048 + 256 + 8388608>, false, {}}};
+            {"no-epi G4 pd1", run<1, 2048 + 256, 4>, false, {}}};
   } else if (getenv("VS_ABL_SET") && !strcmp(getenv("VS_ABL_SET"), "lists")) {
     // r04: the sorted-list pass (MODE 8: per-query top-k lists in LDS, no
     // sample pass, no select: a merge of nwg lists instead) at large shards,
-    // unbounded and pinned, against the candidate main pass
+    // unbounded and bounded, against the candidate main pass
     arms = {{"main (product)", run<0, 2048 + 256, 2>, true, {}},
             {"lists", run<8, 0, 2>, false, {}},
-            {"lists pinned", run<8, 128, 2>, false, {}},
             {"lists 24k", run<8, 2048, 2>, false, {}},
             {"lists bounded", run<8, 0, 2>, true, {}}};
   } else if (getenv("VS_ABL_SET") && !strcmp(getenv("VS_ABL_SET"), "qmax")) {
@@ -235,37 +188,20 @@ int main(int argc, char** argv) {
   } else if (getenv("VS_ABL_SET") && !strcmp(getenv("VS_ABL_SET"), "product")) {
     // the product main pass alone (sample-tile sweeps: argv[3])
     arms = {{"main (product)", run<0, 2048 + 256, 2>, true, {}}};
-  } else if (getenv("VS_ABL_SET") && !strcmp(getenv("VS_ABL_SET"), "barrier")) {
-    // timing only: without the barrier the ring is unsynchronised (wrong
-    // results, no hazard to the device: no waits depend on the data)
-    arms = {{"main (product)", run<0, 2048 + 256, 2>, true, {}},
-            {"no-epi (product)", run<1, 2048 + 256, 2>, false, {}},
-            {"no-epi no-barrier", run<1, 2048 + 256 + 134217728, 2>, false, {}},
-            {"no-epi 16k", run<1, 0, 2>, false, {}},
-            {"no-epi 16k no-barrier", run<1, 134217728, 2>, false, {}}};
   } else if (getenv("VS_ABL_SET") && !strcmp(getenv("VS_ABL_SET"), "chunk")) {
     arms = {{"main bf", run<0, 0, 2>, true, {}},
             {"24k ring144", run<0, 2048 + 256, 2>, true, {}},
-            {"48k ring144", run<0, 4096 + 256, 2>, true, {}},
             {"ring144", run<0, 256, 2>, true, {}}};
-  } else if (getenv("VS_ABL_SET") && !strcmp(getenv("VS_ABL_SET"), "pd")) {
-    arms = {{"main bf", run<0, 0, 2>, true, {}},
-            {"PD2", run<0, 32, 2>, true, {}}};  // r02: 3.325 vs 3.340 ms, 0.426 vs 0.427 (noise)
   } else if (getenv("VS_ABL_SET") && !strcmp(getenv("VS_ABL_SET"), "lds")) {
+    // the 16 KiB-chunk main pass against its no-epilogue and stream-only forms
     arms = {{"main bf", run<0, 0, 2>, true, {}},
-            {"PD2", run<0, 32, 2>, true, {}},
             {"no-epilogue", run<1, 0, 2>, false, {}},
-            {"half A reads (10)", run<10, 0, 2>, false, {}},
-            {"half A, all MFMA (13)", run<13, 0, 2>, false, {}},
-            {"no A reads (7)", run<7, 0, 2>, false, {}},
             {"dma-only", run<2, 0, 2>, false, {}}};
   } else if (!getenv("VS_ABL_SHORT")) {
-    arms.push_back({"main weighted", run<0, 65536, 2>, true, {}});
+    arms.push_back({"main weighted", run_weighted<0, 0, 2>, true, {}});
     arms.push_back({"no-epilogue", run<1, 0, 2>, false, {}});
     arms.push_back({"max-only (6)", run<6, 0, 2>, true, {}});
     arms.push_back({"dma-only", run<2, 0, 2>, false, {}});
-    arms.push_back({"qf-only", run<12, 0, 2>, false, {}});
-    arms.push_back({"G4 no-epi pd3pin", run<1, 64 + 128, 4>, false, {}});
   }
 
   // arms rotate their position every rep: a fixed order measured position
@@ -450,10 +386,6 @@ int main(int argc, char** argv) {
     for (int burst : {1, 8}) {
       if (clocks("sample", mfma_topk_kernel<768, 3, 8192, 2>, sa, burst)) return 1;
       if (clocks("main", mfma_topk_kernel<768, 0, 8192, 2>, ma, burst)) return 1;
-      if (getenv("VS_ABL_SET") && !strcmp(getenv("VS_ABL_SET"), "early")) {
-        if (clocks("sample early", mfma_topk_kernel<768, 3, 8192 + 8388608, 2>, sa, burst)) return 1;
-        if (clocks("main early", mfma_topk_kernel<768, 0, 8192 + 8388608, 2>, ma, burst)) return 1;
-      }
     }
   }
   std::vector<uint32_t> hc((size_t)c.nwg * 256 * 4);

@@ -94,8 +94,6 @@ int main(int argc, char** argv) {
       {"no-epilogue", run<1, 0>, false, {}},
       {"dma-only", run<2, 0>, false, {}},
       {"main ring144", run<0, 256>, true, {}},
-      {"main cached-dma", run<0, 1024>, true, {}},
-      {"main pd3", run<0, 64>, true, {}},
       {"max-only (6)", run<6, 0>, true, {}},
   };
   if (getenv("VS_ABL_ST")) {

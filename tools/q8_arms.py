@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """Timing arms of the int8 prefilter pass (r04): one process per arm, since
-VS_Q8_VAR (the pass's compile-time variant) is read once.
+the engine reads its environment switches once.
 
-    VS_Q8_VAR=2304 python tools/q8_arms.py [--rows 10000000] [--steps 30] [--k 10]
+    python tools/q8_arms.py [--rows 10000000] [--steps 30] [--k 10]
     VS_Q8_SAMPLE=2 python tools/q8_arms.py ...   (sample tiles x2)
 
 Prints one JSON line: the arm, the int8 pass's average HIP-event duration
-(every launch bracketed), ms per step and QPS. No answer is checked (the
-no-append arm returns wrong ones by design); the product arm's answers are
-checked by bench.py and the GPU tests.
+(every launch bracketed), ms per step and QPS. No answer is checked here;
+the product's answers are checked by bench.py and the GPU tests. The pass's
+compile-time variants (ring / chunk geometry, the no-append timing arm) are
+arms of tools/ablate_q8.hip; the library builds the product kernel only.
 """
 import argparse
 import json
@@ -50,7 +51,7 @@ def main():
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
     tm = eng.timing(reset=True)
-    print(json.dumps({"arm": os.environ.get("VS_Q8_VAR", "default"),
+    print(json.dumps({"arm": "default",
                       "sample": os.environ.get("VS_Q8_SAMPLE", "1"), "k": a.k, "dim": a.dim, "rows": a.rows,
                       "prefilter_bytes": eng.prefilter_bytes("b"),
                       "scan_ms": round(tm["scan_ms"], 4), "scans": tm["scan_n"],
