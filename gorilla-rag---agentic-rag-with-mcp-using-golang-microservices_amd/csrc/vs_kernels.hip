@@ -1905,9 +1905,24 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
   constexpr int kCsx = (VAR & 2048) ? 6 : 0;
   // the main pass's LDS words beside the ring: one per lane and query group,
   // the lane's running quarter maximum (mf_quarter_max)
-  constexpr int kCntBytes = MODE == 0 ? 64 * WAVES * G * 4 : 0;
+  constexpr int kCntBytes = MODE == 0 && !I8 ? 64 * WAVES * G * 4 : 0;
+  // The int8 main pass keeps its maxima in registers (qmx_r) and uses the room
+  // beside the ring to stage appended slabs, kStageCap records a wave: the 8
+  // int32 dots (32 B; slab area) and {destination slot or kNoSlot, first row
+  // of the tile} (8 B; meta area). A wave flushes its records to the candidate
+  // buffers in one batch (q8_flush), so the stores leave the tile loop.
+  // Only the one-group pass (1024-d: HBM-bound, where every store among the
+  // ring's pieces slows the stream) stages: -4% there, while the two-group
+  // 768-d pass, bound by MFMA issue, ran level on the product's bound and
+  // +2.6% where appends are frequent (the sample's bound). DESIGN.md §5.
+  constexpr bool kStage = I8 && MODE == 0 && G == 1;
+  constexpr int kStageCap = 48, kStageWave = kStageCap * 40;
+  constexpr int kStageBytes = kStage ? WAVES * kStageWave : 0;
+  static_assert(kStageCap <= 64, "one flush: a lane per record");
+  static_assert(!kStage || !kBigRing || 144 * 1024 + 16 + kStageBytes <= 160 * 1024,
+                "staging area: what the 144 KiB ring leaves of the LDS");
   using S = MfShape<D, kBigRing ? 144 * 1024 : kMfRingBytes,
-                    MODE == 8 ? kMfListBytes : 16 + kCntBytes, WAVES, kCsx, EB>;
+                    MODE == 8 ? kMfListBytes : 16 + kCntBytes + kStageBytes, WAVES, kCsx, EB>;
   constexpr bool kDma = MODE != 4 && MODE != 5;  // decomposition arms without the stream
   constexpr bool kLists = MODE == 8;
   constexpr int PPW = S::PPW;
@@ -2108,7 +2123,7 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
     int v[8];
 #pragma unroll
     for (int b = 0; b < 4; ++b) v[b] = a0[b], v[4 + b] = a1[b];
-    if (!full || a.allow) {  // uniform: unfiltered full tiles skip it
+    if (!full) {  // full: an unfiltered full tile (run_tiles), nothing to mask
       // the row base and mask bits are taken opaque inside the branch: the
       // compiler otherwise hoists their 16 adds/ands into every unfiltered
       // full tile (r05 ISA: 17 of the epilogue's 38 VALU per tile)
@@ -2122,37 +2137,100 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
     }
     return imax3(imax3(v[0], v[1], v[2]), imax3(v[3], v[4], v[5]), imax3(v[6], v[7], INT_MIN));
   };
-  auto q8_epi_app = [&](f32x4_t (&ac)[2][G], int g, uint32_t trow0, int mx) {
-    // VAR 16777216 (tools' timing arm only, wrong answers): never append
-    if ((VAR & 16777216) != 0) {
-      asm volatile("" ::"v"(mx >= th_i[g]));
-      return;
+  // Staged records of this wave (kStage): nst is wave-uniform, so every test on
+  // it is a scalar branch. A wave's records are read only by that wave, and
+  // its LDS operations complete in order: no barrier anywhere.
+  uint32_t nst = 0;
+  constexpr uint32_t kNoSlot = 0xFFFFFFFFu;  // a record of a full quarter: counted, not stored
+  typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+  typedef __attribute__((address_space(3))) volatile f32x4_t lds_vf32x4_t;
+  typedef __attribute__((address_space(3))) volatile u32x2_t lds_vu32x2_t;
+  constexpr int kStageOff = S::NSLOT * S::CHUNK_BYTES + 16;
+  lds_vf32x4_t* const stg_slab = (lds_vf32x4_t*)(lds_ptr_t)(smem + kStageOff + w * kStageWave);
+  lds_vu32x2_t* const stg_meta =
+      (lds_vu32x2_t*)(lds_ptr_t)(smem + kStageOff + w * kStageWave + kStageCap * 32);
+  // Lane r < nst stores record r to its slot: the wave's appends of many
+  // tiles leave in one batch of three stores, outside the tile loop's counted
+  // vmcnt window but for this once.
+  auto q8_flush = [&]() {
+    uint32_t ln = (uint32_t)lane;
+    asm volatile("" : "+v"(ln));  // opaque: no address of this rare path in the tile loop
+    if (ln < nst) {
+      const u32x2_t me = stg_meta[ln];
+      if (me[0] != kNoSlot) {
+        const f32x4_t s0 = stg_slab[2 * ln], s1 = stg_slab[2 * ln + 1];
+        f32x4_t* sp = (f32x4_t*)a.cand + 2 * (size_t)me[0];
+        sp[0] = s0;
+        sp[1] = s1;
+        a.cand_tile[me[0]] = me[1];
+      }
     }
-    if (mx >= th_i[g]) {  // th_i > INT_MIN: padding never passes; invalid queries: INT_MAX
-      const uint32_t sub = a.cand_cap >> 2;
-      const uint32_t cg = cnt_r[g];
-      // r05: a full quarter keeps counting (a count past its capacity
-      // marks it lossy: select_q8 recomputes its rows from the int8
-      // copy) and its largest dot stays exact; no hand-back
-      if (cg < sub) {
+    nst = 0;
+  };
+  // The lanes of group g whose tile maximum mx reaches the threshold
+  // (th_i > INT_MIN: padding never passes; invalid queries: INT_MAX) append
+  // their slabs: staged at nst + their rank among the passing lanes (kStage),
+  // or stored to their slots at once.
+  auto q8_epi_app = [&](f32x4_t (&ac)[2][G], int g, uint32_t trow0, int mx) {
+    const bool pass = mx >= th_i[g];
+    const uint64_t m = __ballot(pass);
+    if (m == 0) return;  // wave-uniform
+    const uint32_t np = (uint32_t)__popcll(m);
+    if constexpr (kStage)
+      if (nst + np > (uint32_t)kStageCap) q8_flush();
+    const uint32_t sub = a.cand_cap >> 2;
+    const uint32_t cg = cnt_r[g];
+    // r05: a full quarter keeps counting (a count past its capacity
+    // marks it lossy: select_q8 recomputes its rows from the int8
+    // copy) and its largest dot stays exact; no hand-back
+    if (!kStage || np > (uint32_t)kStageCap) {
+      // no stage, or more lanes than it holds (no bound, or equal rows):
+      // straight to the buffers, behind the flush
+      if (pass && cg < sub) {
         const size_t slot = (size_t)slot0[g] + cg;
         f32x4_t* sp = (f32x4_t*)a.cand + 2 * slot;
         sp[0] = ac[0][g];
         sp[1] = ac[1][g];
         a.cand_tile[slot] = a.row_base + trow0;
       }
+    } else {
+      if (pass) {
+        const uint32_t pos = nst + __builtin_amdgcn_mbcnt_hi(
+                                       (uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        stg_slab[2 * pos] = ac[0][g];
+        stg_slab[2 * pos + 1] = ac[1][g];
+        stg_meta[pos] = u32x2_t{cg < sub ? slot0[g] + cg : kNoSlot, a.row_base + trow0};
+      }
+      nst += np;
+    }
+    if (pass) {
       cnt_r[g] = cg + 1;
       qmx_r[g] = mx > qmx_r[g] ? mx : qmx_r[g];
     }
   };
+  // full: an unfiltered full tile. Both groups' maxima straight-line, then one
+  // wave-uniform branch around the append code of both.
   auto q8_epi = [&](f32x4_t (&ac)[2][G], uint32_t trow0, bool full) {
     uint32_t am = 0xFFu;
-    if (a.allow) {
+    if (!full && a.allow) {
       const uint32_t tw = (uint32_t)(a.allow[trow0 >> 6] >> (trow0 & 32)) >> (4 * kq);
       am = (tw & 0xFu) | ((tw >> 12) & 0xF0u);
     }
+    int mx[G];
+    bool any = false;
 #pragma unroll
-    for (int g = 0; g < G; ++g) q8_epi_app(ac, g, trow0, q8_epi_mx(ac, g, trow0, full, am));
+    for (int g = 0; g < G; ++g) {
+      mx[g] = q8_epi_mx(ac, g, trow0, full, am);
+      any |= mx[g] >= th_i[g];
+    }
+    // VAR 16777216 (tools' timing arm only, wrong answers): never append
+    if ((VAR & 16777216) != 0) {
+      asm volatile("" ::"v"(any));
+      return;
+    }
+    if (__ballot(any) == 0) return;
+#pragma unroll
+    for (int g = 0; g < G; ++g) q8_epi_app(ac, g, trow0, mx[g]);
   };
   // The one accumulator set lives out here and a tile binds it by reference;
   // the tile loops below stay in lambdas of their own (run_tiles over tile_p
@@ -2380,13 +2458,17 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
   auto tile_p = [&](uint32_t t, auto full_tag) { tile(t, full_tag); };
   auto run_tiles = [&]() {
     if constexpr (kPeel) {
-      for (uint32_t t = 0; t < nfull; ++t) tile_p(t, MfFull<true>{});
-      for (uint32_t t = nfull; t < ntiles; ++t) tile_p(t, MfFull<false>{});
+      // the int8 pass's full-tile body is the unfiltered one: a filtered
+      // launch (uniform) runs every tile through the masking body
+      const uint32_t nf = (I8 && MODE == 0 && a.allow) ? 0u : nfull;
+      for (uint32_t t = 0; t < nf; ++t) tile_p(t, MfFull<true>{});
+      for (uint32_t t = nf; t < ntiles; ++t) tile_p(t, MfFull<false>{});
     } else {
       for (uint32_t t = 0; t < ntiles; ++t) tile_p(t, MfFull<false>{});
     }
   };
   run_tiles();
+  if constexpr (kStage) q8_flush();  // the records still staged
   if constexpr (kDma) wait_vmcnt<0>();  // no LDS-DMA outlives the workgroup
   if constexpr (kClock) tclk2 = wall_clock64();
   // each wave owns its queries' lists / counters: no barrier before the write-out
