@@ -1588,7 +1588,9 @@ hipError_t launch_compact_rows(const uint64_t* allow, uint32_t n_rows, uint32_t*
 // (two per SIMD, 256 queries per launch; D <= 768); G = 1 -> 8 waves of 16
 // queries (128 per launch: the B fragments of D = 1024 / 1536 then fit the
 // 256-register budget); G = 4 (ablation) -> 4 waves of 64 queries (one per
-// SIMD, 512-register budget), which halves the LDS reads per MFMA.
+// SIMD, 512-register budget), which halves the LDS reads per MFMA. The int8
+// pass at G = 2 (768-d) halves them at two waves per SIMD instead: 64 queries
+// x 16 rows a wave (the query-half mapping, kQH in the kernel).
 constexpr int kMfG = 2;
 constexpr int mf_waves(int g) { return g == 4 ? 4 : 8; }
 // query groups per wave from the row bytes: the B fragments of a wave's
@@ -1873,7 +1875,10 @@ struct MfShape {
 // (not MODE 8, whose lists need the room), 2048 = 24 KiB K-chunks (D = 768);
 // the library runs 0 or 256 + 2048 (mf_product_var, launch_mfma_cand_q8).
 // Tools only: 8192 = per-workgroup clocks into a.lists, 16777216 = the int8
-// pass never appends (a timing arm: wrong answers). The experiments that
+// pass never appends (a timing arm: wrong answers), 4096 = the two-group int8
+// pass on the row-major mapping (32 queries x 32 rows a wave) that the
+// query-half mapping below replaced: the same bytes out, twice the LDS
+// reads. The experiments that
 // were measured and taken out of this kernel are listed in DESIGN.md
 // ("Experiments removed from the MFMA scan").
 // F32: fp32 rows and queries on v_mfma_f32_16x16x4_f32 (exact f32 products,
@@ -1884,20 +1889,38 @@ constexpr bool mf_mode_known(int mode) {
   return mode == 0 || mode == 3 || mode == 8 || mode == 1 || mode == 2 || mode == 4 || mode == 5 ||
          mode == 6;
 }
-constexpr bool mf_var_known(int var) { return (var & ~(256 | 2048 | 8192 | 16777216)) == 0; }
+constexpr bool mf_var_known(int var) {
+  return (var & ~(256 | 2048 | 4096 | 8192 | 16777216)) == 0;
+}
 
 template <int D, int MODE = 0, int VAR = 0, int G = mf_groups(D), bool F32 = false, bool I8 = false>
 __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_waves(G)) void mfma_topk_kernel(
     const MfArgs a) {
   static_assert(mf_mode_known(MODE), "MODE: 0, 3, 8 (product) or 1, 2, 4, 5, 6 (decomposition)");
-  static_assert(mf_var_known(VAR), "VAR: only bits 256, 2048, 8192 and 16777216 exist");
+  static_assert(mf_var_known(VAR), "VAR: only bits 256, 2048, 4096, 8192 and 16777216 exist");
   constexpr int WAVES = mf_waves(G), THREADS = 64 * WAVES, QPW = 16 * G;
   constexpr int EB = F32 ? 4 : (I8 ? 1 : 2);
-  static_assert(!I8 || (!F32 && (MODE == 0 || MODE == 1 || MODE == 6)), "int8: the main pass only");
+  static_assert(!I8 || (!F32 && (MODE == 0 || MODE == 1 || MODE == 4 || MODE == 6)),
+                "int8: the main pass only");
   if (a.run_if && *a.run_if == 0u) return;  // uniform: the whole launch stands down
   constexpr int RBY = D * EB;
   static_assert(WAVES * QPW <= (int)kMfmaQueries, "one launch covers <= kMfmaQueries");
-  static_assert(G * (RBY / 64) * 4 <= (mf_waves(G) == 4 ? 400 : 192),
+  // Query-half mapping of the two-group int8 pass (768-d). Waves 2j and 2j+1
+  // both hold queries 64j .. 64j+63 (GB = 4 B groups: 192 VGPRs, the bf16
+  // 768-d pass's budget) and wave parity p takes 16 of a tile's 32 rows as its
+  // A rows: LDS pieces rg = p and rg = 2 + p, i.e. tile rows 8p .. 8p+7 and
+  // 16+8p .. 16+8p+7. A step is ONE ds_read_b128 and four MFMAs (NH = 1 A
+  // fragment), half the LDS reads of the row-major mapping at the same MFMAs.
+  // Lane (col, kq') of the 16x16 output holds A rows 4kq' .. 4kq'+3: lanes
+  // kq' = 0 / 2 hold tile rows 4(2p)+i and 16+4(2p)+i, the two halves of the
+  // slab of quarter 2p, and lanes kq' = 1 / 3 those of quarter 2p+1; so every
+  // (workgroup, query, quarter) slab stream is still written by one wave
+  // (lanes kq' and kq' ^ 2, a 16-B half each), in ascending tile order, into
+  // the same slots: every output word is where it was.
+  constexpr bool kQH = I8 && G == 2 && (VAR & 4096) == 0;
+  constexpr int GB = kQH ? 4 : G;  // 16-query B groups a wave
+  constexpr int NH = kQH ? 1 : 2;  // 16-row A fragments a step
+  static_assert(GB * (RBY / 64) * 4 <= (mf_waves(G) == 4 ? 400 : 192),
                 "B fragments must fit the register budget");
   // VAR 256: a 144 KiB ring (more chunks in flight); LDS lists only in MODE 8
   constexpr bool kBigRing = (VAR & 256) != 0 && MODE != 8;
@@ -2023,35 +2046,56 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
     advance();
   };
   // B operand of group g: Q[query 32w+16g+col][32t + 8kq + j], j = 0..7.
-  bf16x8_t qf[G][S::T];
-  uint32_t ql[G];
-  bool qvalid[G];
-  float th_s[G];     // admit rows whose score reaches th_s
-  int th_i[G];       // I8: admit rows whose int8 dot reaches th_i
+  // (query-half mapping: query 64(w>>1)+16g+col, and the 16-B k slices of a
+  // 128-B piece permuted over (step parity, kq) as the A reads are: qh_chunk)
+  bf16x8_t qf[GB][S::T];
+  uint32_t ql[GB];
+  bool qvalid[GB];
+  float th_s[GB];    // admit rows whose score reaches th_s
+  int th_i[GB];      // I8: admit rows whose int8 dot reaches th_i
   // The main pass keeps the count of slabs this lane appended to its quarter
   // of the query's buffer, and the quarter's first slot, in registers (no LDS
   // round trip and no address rebuild in the append path; 256 VGPRs, no
   // spill: see kNtDma for the measurement against counters in LDS).
   constexpr bool kRegCnt = MODE == 0;
-  uint32_t cnt_r[G], slot0[G];
-  int qmx_r[G];  // I8: the largest dot this lane appended (INT_MIN: none)
+  // The query-half mapping keeps a quarter's count and maximum in both lanes
+  // of its pair (kq and kq ^ 2; the lanes kq < 2 write them out). Its slot
+  // address is ONE register for the four groups, qh_boff: the byte offset,
+  // inside this workgroup's part of the slab buffer (< 8 MiB: cap <= 1024),
+  // of the lane's half (16 B, kq >> 1) of the first slot of quarter
+  // 2 (w & 1) + (kq & 1) of query 64 (w >> 1) + col; group g adds the uniform
+  // 16 g cap slots. A short chain (shift-add, add) ahead of the stores: the
+  // wave in the append body holds the other seven at the next barrier.
+  uint32_t cnt_r[GB], slot0[GB];
+  uint32_t qh_boff = 0;
+  if constexpr (kQH && kRegCnt)
+    qh_boff = ((uint32_t)((w >> 1) * 64 + col) * a.cand_cap +
+               (uint32_t)(2 * (w & 1) + (kq & 1)) * (a.cand_cap >> 2)) * 32u + 16u * (uint32_t)(kq >> 1);
+  int qmx_r[GB];  // I8: the largest dot this lane appended (INT_MIN: none)
+  // Query-half mapping: 16-B chunk of a 128-B piece that lane quarter kq
+  // consumes at step parity tt. Any bijection serves the MFMA (A and B agree);
+  // this one gives kq and kq ^ 1 chunks that differ in bit 2, which is what
+  // keeps the A reads conflict-free now that a lane group's rows share rg & 1
+  // (see off[] below).
+  auto qh_chunk = [&](int tt) -> int { return ((kq & 1) << 2) | (tt << 1) | (kq >> 1); };
 #pragma unroll
-  for (int g = 0; g < G; ++g) {
+  for (int g = 0; g < GB; ++g) {
     qmx_r[g] = INT_MIN;
     // cntl[g * THREADS + tid]: this lane's running quarter maximum,
     // score_ord of the largest admitted score, 0 = none
     if constexpr (kCntBytes > 0) cntl[g * THREADS + threadIdx.x] = 0u;
+    ql[g] = (uint32_t)((kQH ? (w >> 1) * 64 : w * QPW) + g * 16 + col);
     if constexpr (kRegCnt) {
       cnt_r[g] = 0u;
-      slot0[g] = (uint32_t)(((size_t)blockIdx.x * kMfmaQueries +
-                             (uint32_t)(w * QPW + g * 16 + col)) * a.cand_cap +
-                            (uint32_t)kq * (a.cand_cap >> 2));
+      if constexpr (!kQH)
+        slot0[g] = (uint32_t)(((size_t)blockIdx.x * kMfmaQueries + ql[g]) * a.cand_cap +
+                              (uint32_t)kq * (a.cand_cap >> 2));
     }
-    ql[g] = (uint32_t)(w * QPW + g * 16 + col);
     qvalid[g] = ql[g] < a.nq_valid;
     const uint4* qrow = (const uint4*)((const unsigned char*)a.Q + (size_t)ql[g] * RBY);
 #pragma unroll
-    for (int t = 0; t < S::T; ++t) qf[g][t] = __builtin_bit_cast(bf16x8_t, qrow[4 * t + kq]);
+    for (int t = 0; t < S::T; ++t)
+      qf[g][t] = __builtin_bit_cast(bf16x8_t, qrow[kQH ? 8 * (t >> 1) + qh_chunk(t & 1) : 4 * t + kq]);
     th_s[g] = (a.init_score && qvalid[g]) ? a.init_score[ql[g]] : -INFINITY;
     if constexpr (I8) th_i[g] = q8_dot_threshold(a, ql[g], qvalid[g], th_s[g]);
   }
@@ -2065,12 +2109,21 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
 
   // A operand read offsets: half hr (tile rows 16hr..16hr+15), lane reads row
   // 16hr + col, 16-B chunk 4*(t&1) + kq of piece t>>1.
-  int off[2][2];
+  // Query-half mapping: the one fragment's A row col is tile row 8p + col
+  // (col < 8) or 16 + 8p + col - 8, p = w & 1, chunk qh_chunk(tt). A
+  // ds_read_b128 lane group (MI355X: lanes {0-3, 12-15, 20-27} and so on) is
+  // 8 lanes of kq and 8 of kq ^ 1, each set covering ri = 0 .. 7 once; within
+  // a set (ri & 1, chunk ^ (ri >> 1)) gives 8 distinct 16-B bank groups, and
+  // the two sets' chunks differ in bit 2, which no swizzle bit of these rows
+  // (rg & 1 = p for all 16) undoes: 16 distinct bank groups, no conflict.
+  int off[NH][2];
 #pragma unroll
-  for (int hr = 0; hr < 2; ++hr) {
-    const int rr = 16 * hr + col, rg = rr >> 3, ri = rr & 7, sw = mf_swz(ri, rg);
+  for (int hr = 0; hr < NH; ++hr) {
+    const int rr = kQH ? 8 * (w & 1) + (col & 7) + 16 * (col >> 3) : 16 * hr + col;
+    const int rg = rr >> 3, ri = rr & 7, sw = mf_swz(ri, rg);
 #pragma unroll
-    for (int tt = 0; tt < 2; ++tt) off[hr][tt] = rg * 1024 + ri * 128 + (((4 * tt + kq) ^ sw) << 4);
+    for (int tt = 0; tt < 2; ++tt)
+      off[hr][tt] = rg * 1024 + ri * 128 + (((kQH ? qh_chunk(tt) : 4 * tt + kq) ^ sw) << 4);
   }
   auto lds_a = [&](const unsigned char* sb, int s, int hr) -> bf16x8_t {
     return __builtin_bit_cast(bf16x8_t, *(const uint4*)(sb + (s >> 1) * 4096 + off[hr][s & 1]));
@@ -2232,20 +2285,88 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
 #pragma unroll
     for (int g = 0; g < G; ++g) q8_epi_app(ac, g, trow0, mx[g]);
   };
+  // Query-half mapping (kQH): the lane holds 4 of a slab's 8 dots, tile rows
+  // r0 + i (r0 = 16 (kq >> 1) + 8p + 4 (kq & 1)), and lane ^ 32 the other 4.
+  // A slab passes when either half's maximum reaches the threshold, so the
+  // one wave-uniform admission test per tile needs the lane's own max3 chain
+  // only. Inside the rare branch the slab maximum is that and one cross-half
+  // exchange (v_permlane32_swap: VALU, no LDS). Both lanes of a pair see the
+  // same maximum and threshold, so `pass` agrees between them and both keep
+  // the quarter's count and maximum: each stores its own 16-B half of the
+  // slab to the slot (no dot crosses the wave), the lower lane the tile row.
+  // Slab, tile row, count and maximum are the row-major mapping's.
+  auto xhalf_max = [&](int v) -> int {  // max(v, lane ^ 32's v), in both lanes
+    const auto r = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
+    return __builtin_elementwise_max((int)r[0], (int)r[1]);
+  };
+  auto q8h_epi = [&](f32x4_t (&ac)[NH][GB], uint32_t trow0, bool full) {
+    if (!full) {  // padding / filtered rows -> INT_MIN in the slab, as q8_epi_mx
+      uint32_t tid = threadIdx.x;
+      asm volatile("" : "+v"(tid));  // opaque: nothing of this body in the full tiles
+      const uint32_t r0 = 16u * ((tid >> 5) & 1u) + 8u * ((tid >> 6) & 1u) + 4u * ((tid >> 4) & 1u);
+      uint32_t amv = 0xFu;
+      if (a.allow) amv = ((uint32_t)(a.allow[trow0 >> 6] >> (trow0 & 32)) >> r0) & 0xFu;
+      const uint32_t rb = trow0 + r0;
+#pragma unroll
+      for (int g = 0; g < GB; ++g) {
+        const i32x4_t a0 = __builtin_bit_cast(i32x4_t, ac[0][g]);
+        int v[4];
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+          v[b] = (rb + b >= wr1 || !((amv >> b) & 1u)) ? INT_MIN : a0[b];
+        ac[0][g] = __builtin_bit_cast(f32x4_t, i32x4_t{v[0], v[1], v[2], v[3]});
+      }
+    }
+    int mh[GB];  // the lane's half of the slab
+    bool any = false;
+#pragma unroll
+    for (int g = 0; g < GB; ++g) {
+      const i32x4_t a0 = __builtin_bit_cast(i32x4_t, ac[0][g]);
+      mh[g] = imax3(imax3(a0[0], a0[1], a0[2]), a0[3], INT_MIN);
+      any |= mh[g] >= th_i[g];
+    }
+    // VAR 16777216 (tools' timing arm only, wrong answers): never append
+    if ((VAR & 16777216) != 0) {
+      asm volatile("" ::"v"(any));
+      return;
+    }
+    if (__ballot(any) == 0) return;
+#pragma unroll
+    for (int g = 0; g < GB; ++g) {
+      if (__ballot(mh[g] >= th_i[g]) == 0) continue;  // wave-uniform
+      const int mxg = xhalf_max(mh[g]);
+      const bool pass = mxg >= th_i[g];
+      if (pass) {
+        const uint32_t sub = a.cand_cap >> 2;
+        const uint32_t cg = cnt_r[g];
+        // r05: a full quarter keeps counting (lossy: the select recomputes it)
+        if (cg < sub) {
+          // uniform bases of this workgroup's slabs and tile words; the slot in
+          // the workgroup is boff >> 5 (boff & 16: the upper half's lane)
+          const size_t wg0 = (size_t)blockIdx.x * kMfmaQueries * a.cand_cap;
+          const uint32_t boff = qh_boff + (((uint32_t)g * 16u * a.cand_cap + cg) << 5);
+          *(f32x4_t*)((unsigned char*)((f32x4_t*)a.cand + 2 * wg0) + boff) = ac[0][g];
+          if (kq < 2) (a.cand_tile + wg0)[boff >> 5] = a.row_base + trow0;
+        }
+        cnt_r[g] = cg + 1;
+        qmx_r[g] = mxg > qmx_r[g] ? mxg : qmx_r[g];
+      }
+    }
+  };
   // The one accumulator set lives out here and a tile binds it by reference;
   // the tile loops below stay in lambdas of their own (run_tiles over tile_p
   // over tile). Neither is free to change: hipcc optimises each lambda before
   // it inlines it, and with the set local to the tile, or the loops written
   // straight into the kernel, every pass comes out with other code
   // (compared by assembly).
-  f32x4_t acc_set[2][G];
+  f32x4_t acc_set[NH][GB];
   auto tile = [&](uint32_t t, auto full_tag) {
-    f32x4_t (&acc)[2][G] = acc_set;  // [row half][query group]
+    f32x4_t (&acc)[NH][GB] = acc_set;  // [row half][query group]
 #pragma unroll
-    for (int hr = 0; hr < 2; ++hr)
+    for (int hr = 0; hr < NH; ++hr)
 #pragma unroll
-      for (int g = 0; g < G; ++g) acc[hr][g] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    bf16x8_t afr[NB][2];
+      for (int g = 0; g < GB; ++g) acc[hr][g] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    bf16x8_t afr[NB][NH];
 #pragma unroll
     for (int u = 0; u < S::CPT; ++u) {
       const uint32_t c = t * S::CPT + u;
@@ -2255,7 +2376,7 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
       const unsigned char* sbn = smem + snxt;
       if (MODE != 2 && u == 0) {
 #pragma unroll
-        for (int hr = 0; hr < 2; ++hr) afr[0][hr] = lds_a(sb, 0, hr);
+        for (int hr = 0; hr < NH; ++hr) afr[0][hr] = lds_a(sb, 0, hr);
       }
       const bool refill = kDma && c + S::AHEAD < nchunks;  // else the dummy
       __builtin_amdgcn_sched_barrier(0);
@@ -2271,7 +2392,7 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
           // prefetch step sig + 1 (this chunk or the next one)
           if (sig + 1 < STEPS) {
 #pragma unroll
-            for (int hr = 0; hr < 2; ++hr)
+            for (int hr = 0; hr < NH; ++hr)
               afr[(sig + 1) % NB][hr] = s + 1 < S::CT ? lds_a(sb, s + 1, hr) : lds_a(sbn, 0, hr);
           }
           if constexpr (kPin) __builtin_amdgcn_sched_barrier(0);
@@ -2281,10 +2402,10 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
 #pragma unroll
             for (int j = 0; j < 4; ++j)
 #pragma unroll
-              for (int hr = 0; hr < 2; ++hr) {
+              for (int hr = 0; hr < NH; ++hr) {
                 const f32x4_t av = __builtin_bit_cast(f32x4_t, afr[sig % NB][hr]);
 #pragma unroll
-                for (int g = 0; g < G; ++g) {
+                for (int g = 0; g < GB; ++g) {
                   const f32x4_t bv = __builtin_bit_cast(f32x4_t, qf[g][u * S::CT + s]);
                   acc[hr][g] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], bv[j], acc[hr][g], 0, 0,
                                                                     0);
@@ -2292,10 +2413,10 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
               }
           } else {
 #pragma unroll
-            for (int hr = 0; hr < 2; ++hr) {
+            for (int hr = 0; hr < NH; ++hr) {
               const bf16x8_t av = afr[sig % NB][hr];
 #pragma unroll
-              for (int g = 0; g < G; ++g) {
+              for (int g = 0; g < GB; ++g) {
                 if constexpr (I8)  // 64 int8 k per step; exact int32 sums (bits kept in acc)
                   acc[hr][g] = __builtin_bit_cast(
                       f32x4_t, __builtin_amdgcn_mfma_i32_16x16x64_i8(
@@ -2315,9 +2436,9 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
     }
     if constexpr (MODE == 1 || MODE == 2 || MODE == 4 || MODE == 5) {  // no epilogue
 #pragma unroll
-      for (int hr = 0; hr < 2; ++hr)
+      for (int hr = 0; hr < NH; ++hr)
 #pragma unroll
-        for (int g = 0; g < G; ++g) asm volatile("" ::"v"(acc[hr][g][hr * 2 + (g & 1)]));
+        for (int g = 0; g < GB; ++g) asm volatile("" ::"v"(acc[hr][g][hr * 2 + (g & 1)]));
       return;
     }
     // epilogue: acc[hr][g][i] = score(row trow0 + 16hr + 4kq + i, query ql[g])
@@ -2344,11 +2465,14 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
       }
     }
     if constexpr (I8 && MODE == 0) {
-      q8_epi(acc, trow0, full);
+      if constexpr (kQH)
+        q8h_epi(acc, trow0, full);
+      else
+        q8_epi(acc, trow0, full);
       return;
     } else if constexpr (I8) {
 #pragma unroll
-      for (int g = 0; g < G; ++g) asm volatile("" ::"v"(acc[0][g][0]), "v"(acc[1][g][3]));
+      for (int g = 0; g < GB; ++g) asm volatile("" ::"v"(acc[0][g][0]), "v"(acc[NH - 1][g][3]));
       return;
     }
 #pragma unroll
@@ -2473,8 +2597,15 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
   if constexpr (kClock) tclk2 = wall_clock64();
   // each wave owns its queries' lists / counters: no barrier before the write-out
 #pragma unroll
-  for (int g = 0; g < G; ++g) {
-    if constexpr (MODE == 0) {
+  for (int g = 0; g < GB; ++g) {
+    if constexpr (MODE == 0 && kQH) {
+      // lanes kq and kq ^ 2 hold the same words of quarter 2p + (kq & 1) of query ql[g]
+      if (kq < 2) {
+        const size_t ci = ((size_t)ql[g] * gridDim.x + blockIdx.x) * 4 + 2 * (w & 1) + kq;
+        a.cand_cnt[ci] = cnt_r[g];
+        if (a.cand_max) a.cand_max[ci] = (uint32_t)qmx_r[g];
+      }
+    } else if constexpr (MODE == 0) {
       // the int8 pass writes its counts and maxima query-major ([query][wg][4],
       // r05: select_q8 reads a query's 4 nwg quarters in one coalesced load)
       const size_t ci = I8 ? ((size_t)ql[g] * gridDim.x + blockIdx.x) * 4 + kq

@@ -10,6 +10,11 @@
 //   mfma     the same in MODE 4: MFMAs (16x16x32 bf16, 16 cycles each: the
 //            int8 pass's count and cycles) + LDS reads + barriers, no stream
 //   mfma-nb  MODE 5: MODE 4 without barriers
+//   mfma8    the int8 instance itself in MODE 4 (its own LDS reads and MFMAs)
+//   *-rm     prod, noapp, noepi and mfma8 on the row-major mapping the
+//            query-half mapping replaced (VAR 4096: 32 queries x 32 rows a
+//            wave, two ds_read_b128 a step; the same bytes out). The library
+//            launches the query-half kernel only.
 // noepi and stream use the product's branch-free stream, as every mode of the
 // kernel that streams. The experiment arms once timed here (pair, epipipe,
 // spread, prea, split, pd2/pd3, stag, pair+epi, the sample pass's early ring
@@ -124,6 +129,11 @@ int main(int argc, char** argv) {
       {"stream", run<384, 2, 2304, false>, {}},
       {"mfma", run<384, 4, 2304, false>, {}},
       {"mfma-nb", run<384, 5, 2304, false>, {}},
+      {"mfma8", run<768, 4, 2304, true>, {}},
+      {"prod-rm", run<768, 0, 2304 + 4096, true>, {}},
+      {"noapp-rm", run<768, 0, 2304 + 4096 + 16777216, true>, {}},
+      {"noepi-rm", run<768, 1, 2304 + 4096, true>, {}},
+      {"mfma8-rm", run<768, 4, 2304 + 4096, true>, {}},
   };
   // an arm's name as the 4th argument: that arm alone (PMC passes), R x B launches
   if (argc > 4) {
@@ -195,6 +205,32 @@ int main(int argc, char** argv) {
       std::sort(v.begin(), v.end());
       printf(", \"sample_clk_%s_us_med\": %.2f, \"sample_clk_%s_us_max\": %.2f", nm[j], v[v.size() / 2], nm[j],
              v.back());
+    }
+  }
+  // the int8 pass's own clocks, both mappings (the query-half prologue loads
+  // 64 queries' fragments a wave, the row-major one 32)
+  {
+    uint64_t* clkb;
+    CK(hipMalloc(&clkb, (size_t)c.nwg * 4 * 8));
+    MfArgs qa = c.q8;
+    qa.lists = clkb;
+    for (int rm = 0; rm < 2; ++rm) {
+      for (int i = 0; i < 3; ++i) {
+        if (rm)
+          hipLaunchKernelGGL((mfma_topk_kernel<768, 0, 2304 + 4096 + 8192, 2, false, true>), dim3(c.nwg),
+                             dim3(512), 0, 0, qa);
+        else
+          hipLaunchKernelGGL((mfma_topk_kernel<768, 0, 2304 + 8192, 2, false, true>), dim3(c.nwg), dim3(512),
+                             0, 0, qa);
+      }
+      CK(hipDeviceSynchronize());
+      std::vector<uint64_t> h((size_t)c.nwg * 4);
+      CK(hipMemcpy(h.data(), clkb, h.size() * 8, hipMemcpyDeviceToHost));
+      std::vector<double> v;  // prologue: start -> fragments and bounds loaded, per workgroup
+      for (uint32_t b = 0; b < c.nwg; ++b) v.push_back((h[4 * b + 1] - h[4 * b]) * 0.01);
+      std::sort(v.begin(), v.end());
+      printf(", \"q8%s_clk_prologue_us_med\": %.2f, \"q8%s_clk_prologue_us_max\": %.2f", rm ? "-rm" : "",
+             v[v.size() / 2], rm ? "-rm" : "", v.back());
     }
   }
   printf("}\n");
