@@ -6,6 +6,8 @@ import (
 	"fmt"
 	"log"
 	"net/http"
+	"reflect"
+	"sort"
 	"sync"
 
 	"gorilla-rag/vsearch"
@@ -208,6 +210,110 @@ func (s *service) upsert(w http.ResponseWriter, r *http.Request) {
 	st.mu.Unlock()
 	writeJSON(w, http.StatusOK, map[string]interface{}{
 		"status": "success", "collection": body.Collection, "points": n})
+}
+
+type deleteBody struct {
+	Collection string                 `json:"collection"`
+	IDs        []interface{}          `json:"ids"`
+	Filter     map[string]interface{} `json:"filter"`
+}
+
+// remove serves POST /delete, an extension outside the reference's four
+// routes (Qdrant's Points.Delete has no call site there): the points named by
+// "ids", or those whose payload holds every "filter" key with an equal value,
+// go through Engine.Delete, and the store is renumbered from the moves under
+// the collection's writer lock (search holds the reader lock through its
+// decode, so an answer belongs to one version). Unknown ids are ignored.
+func (s *service) remove(w http.ResponseWriter, r *http.Request) {
+	if r.Method != http.MethodPost {
+		http.Error(w, "Method not allowed", http.StatusMethodNotAllowed)
+		return
+	}
+	var body deleteBody
+	if err := json.NewDecoder(r.Body).Decode(&body); err != nil {
+		writeError(w, http.StatusBadRequest, "Invalid request body")
+		return
+	}
+	if body.Collection == "" {
+		writeError(w, http.StatusBadRequest, "Collection name required")
+		return
+	}
+	if (body.IDs != nil) == (body.Filter != nil) {
+		writeError(w, http.StatusBadRequest, "Exactly one of ids and filter must be given")
+		return
+	}
+	if body.Filter != nil && len(body.Filter) == 0 { // it would match every point
+		writeError(w, http.StatusBadRequest, "filter must not be empty")
+		return
+	}
+	ids := make([]string, len(body.IDs))
+	for i, v := range body.IDs {
+		id, ok := v.(string)
+		if !ok {
+			writeError(w, http.StatusBadRequest, "Point ID must be a string")
+			return
+		}
+		ids[i] = id
+	}
+	st := s.store(body.Collection)
+	if st == nil {
+		writeError(w, http.StatusInternalServerError, "Failed to delete: collection "+
+			body.Collection+" not found")
+		return
+	}
+	for i := range ids {
+		c, ok := canonicalUUID(ids[i])
+		if !ok {
+			writeError(w, http.StatusInternalServerError, "Failed to delete: Unable to parse UUID: "+ids[i])
+			return
+		}
+		ids[i] = c
+	}
+	st.mu.Lock()
+	defer st.mu.Unlock()
+	var rows []uint64
+	if body.IDs != nil {
+		seen := map[uint64]bool{}
+		for _, id := range ids {
+			if row, ok := st.rowOf[id]; ok && !seen[row] {
+				seen[row] = true
+				rows = append(rows, row)
+			}
+		}
+		sort.Slice(rows, func(a, b int) bool { return rows[a] < rows[b] })
+	} else {
+		for row, pl := range st.payloads {
+			match := true
+			for k, v := range body.Filter {
+				if got, ok := pl[k]; !ok || !reflect.DeepEqual(got, v) {
+					match = false
+					break
+				}
+			}
+			if match {
+				rows = append(rows, uint64(row))
+			}
+		}
+	}
+	if len(rows) > 0 {
+		from, to, err := s.eng.Delete(body.Collection, rows)
+		if err != nil {
+			msg := "Failed to delete: " + err.Error()
+			// the engine compacted the rows but the moves were lost: the ids here no
+			// longer match its rows, so the collection is emptied on both sides
+			if _, now, ierr := s.eng.Info(body.Collection); ierr == nil && now != uint64(len(st.ids)) {
+				_ = s.eng.Drop(body.Collection)
+				_ = s.eng.Create(body.Collection, s.dim, vsearch.MetricCosine, s.dtype, 0)
+				st.rowOf, st.ids, st.payloads = map[string]uint64{}, nil, nil
+				msg += " (the collection was emptied)"
+			}
+			writeError(w, http.StatusInternalServerError, msg)
+			return
+		}
+		st.remove(rows, from, to)
+	}
+	writeJSON(w, http.StatusOK, map[string]interface{}{
+		"status": "success", "collection": body.Collection, "deleted": len(rows)})
 }
 
 type searchBody struct {

@@ -87,6 +87,7 @@ func main() {
 	mux.HandleFunc("/collections", svc.collections)
 	mux.HandleFunc("/upsert", svc.upsert)
 	mux.HandleFunc("/search", svc.search)
+	mux.HandleFunc("/delete", svc.remove) // an extension: the reference has no delete route
 
 	port := env("PORT", "8082")
 	log.Printf("Vector Service starting on port %s (engine: vsearch-hip, devices %s)", port,

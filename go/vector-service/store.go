@@ -94,6 +94,22 @@ func (p *pointStore) commit(ids []string, rows []uint64, payloads []map[string]i
 	}
 }
 
+// remove renumbers the store after the engine deleted `rows` (distinct) and
+// moved row from[i] to row to[i] (vsearch.Engine.Delete: from[i] is at or
+// past the new row count, to[i] below it). Writer lock held.
+func (p *pointStore) remove(rows, from, to []uint64) {
+	for _, r := range rows {
+		delete(p.rowOf, p.ids[r])
+	}
+	for i := range from {
+		p.rowOf[p.ids[from[i]]] = to[i]
+		p.ids[to[i]] = p.ids[from[i]]
+		p.payloads[to[i]] = p.payloads[from[i]]
+	}
+	n := len(p.ids) - len(rows)
+	p.ids, p.payloads = p.ids[:n], p.payloads[:n]
+}
+
 // sidecar is the store's snapshot next to the engine's rows.
 type sidecar struct {
 	IDs      []string                 `json:"ids"`

@@ -56,6 +56,10 @@ static int vsg_upsert(vs_engine* h, const char* n, uint64_t cnt, uint32_t d, con
                       const float* v, vsg_err* e) {
 	return vsg_fin(vs_upsert(h, n, cnt, d, r, v), e);
 }
+static int vsg_delete(vs_engine* h, const char* n, uint64_t cnt, const uint64_t* r, uint64_t* from,
+                      uint64_t* to, uint64_t* moved, vsg_err* e) {
+	return vsg_fin(vs_delete(h, n, cnt, r, from, to, moved), e);
+}
 static int vsg_generate(vs_engine* h, const char* n, uint64_t cnt, uint64_t seed, vsg_err* e) {
 	return vsg_fin(vs_generate(h, n, cnt, seed), e);
 }
@@ -313,6 +317,30 @@ func (e *Engine) Upsert(name string, dim uint32, rows []uint64, vecs []float32) 
 	var ce C.vsg_err
 	return check(C.vsg_upsert(e.h, cs, C.uint64_t(len(rows)), C.uint32_t(dim),
 		(*C.uint64_t)(unsafe.Pointer(&rows[0])), (*C.float)(unsafe.Pointer(&vecs[0])), &ce), &ce)
+}
+
+// Delete removes rows (repeats count once) by compaction (vs_delete): the
+// surviving tail rows move into the holes and the collection is truncated to
+// rows - distinct(rows). It returns the moves: the stored row from[i] is now
+// row to[i]. The caller renumbers its ids and payloads from them, as Upsert
+// leaves ids to the caller. Qdrant's Points.Delete; the reference never
+// calls it.
+func (e *Engine) Delete(name string, rows []uint64) (from, to []uint64, err error) {
+	if len(rows) == 0 {
+		return nil, nil, nil
+	}
+	cs := C.CString(name)
+	defer C.free(unsafe.Pointer(cs))
+	from = make([]uint64, len(rows))
+	to = make([]uint64, len(rows))
+	var moved C.uint64_t
+	var ce C.vsg_err
+	if err = check(C.vsg_delete(e.h, cs, C.uint64_t(len(rows)),
+		(*C.uint64_t)(unsafe.Pointer(&rows[0])), (*C.uint64_t)(unsafe.Pointer(&from[0])),
+		(*C.uint64_t)(unsafe.Pointer(&to[0])), &moved, &ce), &ce); err != nil {
+		return nil, nil, err
+	}
+	return from[:moved], to[:moved], nil
 }
 
 // Generate appends n synthetic unit rows made on the device (benchmarks).

@@ -25,6 +25,12 @@
 
 using vsjson::Json;
 
+// vs_delete is referenced weakly: an engine library without it (an older
+// build, or a test double of the C-ABI) still loads, and /delete answers 501.
+extern "C" int vs_delete(vs_engine* eng, const char* coll, uint64_t n, const uint64_t* rows,
+                         uint64_t* moved_from, uint64_t* moved_to, uint64_t* n_moved)
+    __attribute__((weak));
+
 namespace {
 
 struct CollState {
@@ -438,6 +444,45 @@ std::string decode_upsert(const char* body, size_t len, UpsertRequest* req) {
   return first;
 }
 
+struct DeleteRequest {  // the /delete extension (include/vsearch_service.h)
+  std::string collection;
+  bool has_ids = false, has_filter = false;
+  std::vector<const Json*> ids;  // nullptr = an element that is not a string
+  Json filter;
+  Json root;
+};
+
+std::string decode_delete(const char* body, size_t len, DeleteRequest* req) {
+  std::string err;
+  if (!vsjson::parse(body, len, &req->root, &err)) return err;
+  const Json& root = req->root;
+  if (root.kind == Json::Null) return "";
+  if (root.kind != Json::Object) return "cannot unmarshal into DeleteRequest";
+  std::string first;
+  if (const Json* c = root.field("collection")) {
+    if (c->kind == Json::String) req->collection = c->str;
+    else if (c->kind != Json::Null && first.empty()) first = "collection: not a string";
+  }
+  if (const Json* p = root.field("ids")) {
+    if (p->kind == Json::Array) {
+      req->has_ids = true;
+      for (const auto& e : p->arr) req->ids.push_back(e.kind == Json::String ? &e : nullptr);
+    } else if (p->kind != Json::Null && first.empty()) {
+      first = "ids: not an array";
+    }
+  }
+  if (const Json* f = root.field("filter")) {
+    if (f->kind == Json::Object) {
+      if (!interface_numbers_ok(*f) && first.empty()) first = "filter: number out of range";
+      req->has_filter = true;
+      req->filter = *f;
+    } else if (f->kind != Json::Null && first.empty()) {
+      first = "filter: not an object";
+    }
+  }
+  return first;
+}
+
 // convertVector (main.go:343-375) for a decoded interface{}
 bool convert_vector(const Json& v, std::vector<float>* out, std::string* err) {
   if (v.kind != Json::Array) {
@@ -754,6 +799,107 @@ Response handle_search(vsvc* svc, const std::string& method, const char* body, s
   out.append("}\n");
   Response r;
   r.body = std::move(out);
+  return r;
+}
+
+// POST /delete (an extension: the reference has no delete route). Removes the
+// points named by "ids", or those whose payload matches "filter" (the matcher
+// of "filter":"match", whatever the service's filter setting), through
+// vs_delete, and renumbers the host half of the store from the pairs it
+// returns. The collection's writer lock is held throughout, and /search holds
+// the reader lock through its id / payload decode, so every answer belongs to
+// one version of the collection.
+Response handle_delete(vsvc* svc, const std::string& method, const char* body, size_t len) {
+  if (method != "POST") return error_text("Method not allowed", 405);
+  DeleteRequest req;
+  if (!decode_delete(body, len, &req).empty()) return error_json("Invalid request body", 400);
+  if (req.collection.empty()) return error_json("Collection name required", 400);
+  if (req.has_ids == req.has_filter)
+    return error_json("Exactly one of ids and filter must be given", 400);
+  // an empty conjunction matches every point: not a way to empty a collection
+  if (req.has_filter && req.filter.obj.empty())
+    return error_json("filter must not be empty", 400);
+  for (const Json* id : req.ids)
+    if (!id) return error_json("Point ID must be a string", 400);
+  if (!vs_delete) return error_json("Delete is not supported by this engine", 501);
+
+  auto cs = svc->find(req.collection);
+  if (!cs) return error_json("Failed to delete: " + not_found(req.collection), 500);
+  std::vector<std::string> canon(req.ids.size());
+  for (size_t i = 0; i < req.ids.size(); ++i)
+    if (!canonical_uuid(req.ids[i]->str, &canon[i]))
+      return error_json("Failed to delete: " + grpc_error(VS_ERR_INVALID_ARG,
+                                                          "Unable to parse UUID: " + req.ids[i]->str),
+                        500);
+
+  std::unique_lock<std::shared_mutex> wl(cs->mu);
+  // bulk-generated points keep invertible synthetic ids and no per-row state
+  // to renumber: a benchmark device, not a store to delete from
+  if (cs->bulk) return error_json("collection holds bulk-generated points", 400);
+  std::vector<uint64_t> rows;
+  if (req.has_ids) {
+    for (const auto& c : canon) {  // unknown ids are ignored, as Qdrant ignores them
+      auto it = cs->row_of.find(c);
+      if (it != cs->row_of.end()) rows.push_back(it->second);
+    }
+    std::sort(rows.begin(), rows.end());
+    rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
+  } else {
+    for (uint64_t i = 0; i < cs->payload_of.size(); ++i)
+      if (payload_matches(cs->payload_of[i], req.filter)) rows.push_back(i);
+  }
+  if (!rows.empty()) {
+    std::vector<uint64_t> from(rows.size()), to(rows.size());
+    uint64_t moved = 0;
+    const int rc = vs_delete(svc->eng, req.collection.c_str(), rows.size(), rows.data(),
+                             from.data(), to.data(), &moved);
+    if (rc != VS_OK) {
+      const std::string msg = "Failed to delete: " + grpc_error(rc, last_error());
+      // A device failure after the engine compacted the rows loses the pairs,
+      // and the ids here no longer match the engine's rows: serving them would
+      // answer searches with other points' ids. The collection is emptied on
+      // both sides instead (its points have to be ingested again).
+      uint64_t now = 0;
+      uint32_t dim = 0;
+      int metric = 0, dtype = 0;
+      if (vs_collection_info(svc->eng, req.collection.c_str(), &dim, &now, &metric, &dtype) ==
+              VS_OK &&
+          now != cs->nrows()) {
+        (void)vs_collection_drop(svc->eng, req.collection.c_str());
+        (void)vs_collection_create(svc->eng, req.collection.c_str(), dim, metric, dtype, 0, 0);
+        cs->row_of.clear();
+        cs->uuid_of.clear();
+        cs->payload_of.clear();
+        ++cs->version;
+        std::lock_guard<std::mutex> g(cs->fmu);
+        cs->fcache.clear();
+        return error_json(msg + " (the collection was emptied)", 500);
+      }
+      return error_json(msg, 500);
+    }
+    for (uint64_t r : rows) cs->row_of.erase(cs->uuid_of[r]);
+    for (uint64_t i = 0; i < moved; ++i) {  // from[i] >= the new count > to[i]
+      cs->row_of[cs->uuid_of[from[i]]] = to[i];
+      cs->uuid_of[to[i]] = std::move(cs->uuid_of[from[i]]);
+      cs->payload_of[to[i]] = std::move(cs->payload_of[from[i]]);
+    }
+    cs->uuid_of.resize(cs->uuid_of.size() - rows.size());
+    cs->payload_of.resize(cs->uuid_of.size());
+    ++cs->version;  // cached filter masks name the old rows
+    std::lock_guard<std::mutex> g(cs->fmu);
+    for (auto& kv : cs->fcache)  // the engine dropped them with the delete
+      if (kv.second.device_id) (void)vs_filter_drop(svc->eng, kv.second.device_id);
+    cs->fcache.clear();
+  }
+  wl.unlock();
+
+  Json o = Json::object();
+  o.obj.emplace_back("status", Json::string("success"));
+  o.obj.emplace_back("collection", Json::string(req.collection));
+  o.obj.emplace_back("deleted", Json::number((double)rows.size()));
+  Response r;
+  vsjson::encode(o, &r.body);  // keys sorted, as /upsert's reply
+  r.body.push_back('\n');
   return r;
 }
 
@@ -1095,6 +1241,7 @@ int vsvc_handle(vsvc* svc, const char* method, const char* path, const char* bod
   else if (p == "/collections") r = handle_collections(svc, m);
   else if (p == "/upsert") r = handle_upsert(svc, m, body, body_len);
   else if (p == "/search") r = handle_search(svc, m, body, body_len);
+  else if (p == "/delete") r = handle_delete(svc, m, body, body_len);
   else r = error_text("404 page not found", 404);
   *status = r.status;
   *resp = dup_bytes(r.body);
@@ -1160,6 +1307,9 @@ int vsvc_validate(const char* path, const char* body, size_t len, char** msg) {
   } else if (p == "/upsert") {
     UpsertRequest r;
     err = decode_upsert(body ? body : "", len, &r);
+  } else if (p == "/delete") {
+    DeleteRequest r;
+    err = decode_delete(body ? body : "", len, &r);
   }
   if (msg) *msg = dup_bytes(err);
   return err.empty() ? 0 : 400;

@@ -872,6 +872,83 @@ int sharded_generate(vs_engine* E, const char* coll, uint64_t n, uint64_t seed) 
   return VS_OK;
 }
 
+// vs_delete on a multi-shard engine. A placed collection deletes on its
+// device. A row-striped one applies the rule in global rows on the host: all
+// global rows >= N' vanish, so every shard truncates to its share of [0, N'),
+// and the surviving tail rows cross shards through the host as raw stored
+// bytes (deletes are not the hot path).
+int sharded_delete(vs_engine* E, const char* coll, uint64_t n, const uint64_t* rows,
+                   uint64_t* moved_from, uint64_t* moved_to, uint64_t* n_moved) {
+  if (n_moved) *n_moved = 0;
+  auto sc = find_scoll(E, coll);
+  if (!sc) return not_found(coll);
+  auto drop_filters = [&] {  // their bits name the old row numbers
+    std::lock_guard<std::mutex> g(E->filt_mu);
+    for (auto it = E->filters.begin(); it != E->filters.end();)
+      it = it->second.coll_gen == sc->gen ? E->filters.erase(it) : std::next(it);
+  };
+  if (sc->home >= 0) {
+    const int rc = vsd::delete_rows(home_eng(E, *sc), sc->iname[0].c_str(), n, rows, moved_from,
+                                    moved_to, n_moved);
+    if (rc == VS_OK && n) drop_filters();  // the device engine dropped its half
+    return rc;
+  }
+  if (n == 0) return VS_OK;
+  if (!rows || !moved_from || !moved_to || !n_moved)
+    return fail(VS_ERR_INVALID_ARG, "rows, moved_from, moved_to and n_moved are required");
+  std::unique_lock<std::shared_mutex> wl(sc->mu);
+  const uint64_t N = sc->rows;
+  for (uint64_t i = 0; i < n; ++i)
+    if (rows[i] >= N)
+      return fail(VS_ERR_INVALID_ARG, "delete: row " + std::to_string(rows[i]) +
+                                          " is past the collection's " + std::to_string(N) + " rows");
+  std::vector<uint64_t> del(rows, rows + n);
+  std::sort(del.begin(), del.end());
+  del.erase(std::unique(del.begin(), del.end()), del.end());
+  const uint64_t Nn = N - del.size();
+  const size_t p = (size_t)(std::lower_bound(del.begin(), del.end(), Nn) - del.begin());
+  std::vector<uint64_t> from;  // survivors in [Nn, N), ascending; holes = del[0, p)
+  from.reserve(p);
+  for (uint64_t g = Nn, j = p; g < N; ++g) {
+    if (j < del.size() && del[j] == g) ++j;
+    else from.push_back(g);
+  }
+  const uint32_t S = E->shards();
+  const size_t rb = (size_t)sc->dim * (sc->dtype == VS_DTYPE_BF16 ? 2 : 4);
+  // every shard's tail (its local rows of the global rows [Nn, N)), as stored
+  std::vector<std::vector<unsigned char>> tail(S);
+  std::vector<uint64_t> tail_g0(S, 0);
+  for (uint32_t s = 0; s < S && p; ++s) {
+    uint64_t g0, cnt;
+    stripe_range(Nn, N, S, s, &g0, &cnt);
+    tail_g0[s] = g0;
+    if (!cnt) continue;
+    tail[s].resize(cnt * rb);
+    const int rc = vsd::read_raw(shard_eng(E, s), sc->iname[s].c_str(), g0 / S, cnt, tail[s].data());
+    if (rc != VS_OK) return rc;
+  }
+  std::vector<std::vector<uint64_t>> lrows(S);
+  std::vector<std::vector<unsigned char>> lraw(S);
+  for (size_t i = 0; i < p; ++i) {
+    const uint32_t ss = (uint32_t)(from[i] % S), ds = (uint32_t)(del[i] % S);
+    const unsigned char* src = tail[ss].data() + (from[i] - tail_g0[ss]) / S * rb;
+    lrows[ds].push_back(del[i] / S);
+    lraw[ds].insert(lraw[ds].end(), src, src + rb);
+  }
+  for (uint32_t s = 0; s < S; ++s) {
+    uint64_t g0, share;
+    stripe_range(0, Nn, S, s, &g0, &share);
+    const int rc = vsd::delete_apply(shard_eng(E, s), sc->iname[s].c_str(), share, lrows[s].size(),
+                                     lrows[s].data(), lraw[s].data());
+    if (rc != VS_OK) return rc;  // earlier shards are already truncated (as a failed upsert)
+  }
+  sc->rows = Nn;
+  drop_filters();
+  for (size_t i = 0; i < p; ++i) moved_from[i] = from[i], moved_to[i] = del[i];
+  *n_moved = p;
+  return VS_OK;
+}
+
 int sharded_filter_create(vs_engine* E, const char* coll, const uint64_t* allow,
                           uint64_t allow_words, uint64_t* filter_id) {
   if (!allow || !filter_id) return fail(VS_ERR_INVALID_ARG, "NULL argument");
@@ -1192,6 +1269,14 @@ int vs_upsert(vs_engine* eng, const char* coll, uint64_t n, uint32_t dim, const 
   if (!eng) return fail(VS_ERR_INVALID_ARG, "engine is NULL");
   if (!eng->sharded) return vsd::upsert(eng->dev[0], coll, n, dim, rows, vecs);
   return sharded_upsert(eng, coll, n, dim, rows, vecs);
+}
+
+int vs_delete(vs_engine* eng, const char* coll, uint64_t n, const uint64_t* rows,
+              uint64_t* moved_from, uint64_t* moved_to, uint64_t* n_moved) {
+  if (!eng) return fail(VS_ERR_INVALID_ARG, "engine is NULL");
+  if (!eng->sharded)
+    return vsd::delete_rows(eng->dev[0], coll, n, rows, moved_from, moved_to, n_moved);
+  return sharded_delete(eng, coll, n, rows, moved_from, moved_to, n_moved);
 }
 
 int vs_generate(vs_engine* eng, const char* coll, uint64_t n, uint64_t seed) {

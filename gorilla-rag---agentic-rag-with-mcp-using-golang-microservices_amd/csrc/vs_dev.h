@@ -290,6 +290,8 @@ struct DevEngine {
   // completion counter (zeroed at allocation; each launch leaves it zero)
   DevBuf small_part;
   DevBuf q8g;  // one query on the int8 copy: workgroup lists, wave bounds, candidates
+  DevBuf del;  // vs_delete: rows, bitmaps, the pair lists, the tile list, a striped delete's
+               // staged rows; kept between calls up to 64 MiB, released above (delete_rows)
   // (r05) per collection (Collection::gen): what this context has answered
   // on its stream, for the speculative bound (vs_spec_host.h spec_plan)
   SpecSeenMap spec_seen;
@@ -338,6 +340,15 @@ int generate_vectors(DevEngine* eng, uint64_t seed, uint64_t row0, uint64_t n, u
 int read_rows(DevEngine* eng, const char* coll, uint64_t first, uint64_t n, float* out);
 int read_raw(DevEngine* eng, const char* coll, uint64_t first, uint64_t n, void* out);
 int append_raw(DevEngine* eng, const char* coll, uint64_t n, const void* rows);
+// vs_delete on one device's collection (include/vsearch.h states the rule).
+int delete_rows(DevEngine* eng, const char* coll, uint64_t n, const uint64_t* rows,
+                uint64_t* moved_from, uint64_t* moved_to, uint64_t* n_moved);
+// One shard's half of a row-striped delete: `raw` holds n rows as stored, row
+// i of which is written to local row dst_rows[i] (distinct, all < new_rows);
+// then the collection is truncated to new_rows <= its rows, its int8 copy
+// brought in step and its filters dropped, as delete_rows does. n may be 0.
+int delete_apply(DevEngine* eng, const char* coll, uint64_t new_rows, uint64_t n,
+                 const uint64_t* dst_rows, const void* raw);
 int checksum_shard(DevEngine* eng, const char* coll, uint64_t stride, uint64_t offset,
                    uint64_t* out);
 const char* last_error();

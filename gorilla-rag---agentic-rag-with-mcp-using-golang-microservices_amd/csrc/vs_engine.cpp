@@ -203,11 +203,12 @@ bool q8_enabled() {
 // A collection keeps an int8 copy once its batched searches take the
 // candidate pass (8 or more tiles per workgroup) -- q8_supported dims (bf16
 // 768 / 1024, fp32 768).
-bool q8_wanted(const DevEngine* eng, const Collection& c) {
+bool q8_wanted_at(const DevEngine* eng, const Collection& c, uint64_t rows) {
   return q8_enabled() && !(eng->flags & VS_FLAG_NO_PREFILTER) &&
          vsk::q8_supported(c.dim, c.dtype == VS_DTYPE_F32) &&
-         c.rows < 0xFFFFFFFFull && vsk::mfma_tiles_per_wg((uint32_t)c.rows) >= 8;
+         rows < 0xFFFFFFFFull && vsk::mfma_tiles_per_wg((uint32_t)rows) >= 8;
 }
+bool q8_wanted(const DevEngine* eng, const Collection& c) { return q8_wanted_at(eng, c, c.rows); }
 
 uint64_t q8_reserve_bytes(int flags, uint32_t dim, int dtype, uint64_t rows) {
   if (!q8_enabled() || (flags & VS_FLAG_NO_PREFILTER) || rows >= 0xFFFFFFFFull ||
@@ -1608,6 +1609,249 @@ int append_raw(DevEngine* eng, const char* coll, uint64_t n, const void* rows) {
   rc = q8_after_write(eng, *c, c->rows - n, c->rows);
   if (rc != VS_OK) return rc;
   VS_HIP(hipStreamSynchronize(eng->stream), "restore sync");
+  return VS_OK;
+}
+
+// ---- point deletion (include/vsearch.h vs_delete) ---------------------------
+namespace {
+
+// Carves 256-byte aligned regions out of one scratch buffer.
+struct Carve {
+  size_t off = 0;
+  size_t take(size_t bytes) {
+    const size_t at = off;
+    off += (bytes + 255) & ~(size_t)255;
+    return at;
+  }
+};
+
+// The common end of a delete, after the surviving rows were moved on
+// eng->stream (writer lock and work_mu held): the row count is lowered, the
+// int8 copy requantises the nt tiles listed at d_tiles (the tiles that
+// received a row and the one now holding the last row; rows past the new end
+// are written as zeros) and forgets its speculative ratios, and the
+// collection's resident filters, whose bits name the old row numbers, go.
+// glob's dmax / nmax may stay raised: they remain valid bounds. A failure
+// here, or in the tile list's launches before it (`tiles`), leaves the copy
+// behind the rows, so it is dropped (as q8_after_write does) and the delete
+// goes on: the caller still needs its pairs.
+// A collection that shrinks under the size that keeps an int8 copy (q8_wanted)
+// loses it here (`keep` false): the store-side writes maintain the copy only
+// while q8_wanted holds, so a copy kept below that size would fall behind the
+// rows while one-query searches still read it. Growing back rebuilds it whole.
+void delete_finish(DevEngine* eng, Collection& c, uint64_t new_rows, bool keep, hipError_t tiles,
+                   const uint32_t* d_tiles, uint32_t nt) {
+  c.rows = new_rows;
+  if (c.q8 && !keep) {
+    (void)hipStreamSynchronize(eng->stream);
+    c.q8_free();
+  }
+  if (c.q8) {
+    hipError_t e = q8_fail_injected() ? hipErrorUnknown : tiles;
+    if (e == hipSuccess && nt)
+      e = vsk::launch_q8_quantize(c.data, c.dtype == VS_DTYPE_F32, (uint32_t)new_rows, c.dim,
+                                  d_tiles, 0, nt, (int8_t*)c.q8, c.q8_meta, c.q8_glob, eng->stream);
+    if (e == hipSuccess) e = q8_spec_reset(eng, c);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipStreamSynchronize(eng->stream);
+      c.q8_free();
+    }
+  }
+  DevStore& st = *eng->store;
+  std::lock_guard<std::mutex> gf(st.filt_mu);
+  for (auto it = st.filters.begin(); it != st.filters.end();)
+    it = it->second->coll_gen == c.gen ? st.filters.erase(it) : std::next(it);
+}
+
+// The delete scratch is kept between calls up to this size; a larger one (a
+// striped delete stages its moved rows there) is released when the call ends.
+constexpr size_t kDelKeepBytes = 64ull << 20;
+
+// A failure after the rows were compacted: the collection is dense and
+// searchable, but the caller never learns how its rows were renumbered.
+int fail_after_compaction(hipError_t e, const char* what) {
+  (void)fail_hip(e, what);
+  return fail(VS_ERR_DEVICE, std::string(last_error()) +
+                                 "; the rows were already compacted, so the caller's ids no longer "
+                                 "match this collection's rows: drop or restore it");
+}
+
+// Distinct 32-row tiles among dst[0, p) (ascending rows) plus the tile of row
+// new_rows - 1: the length of the list launch_mark_tiles + launch_compact_range
+// build on the device (the host sizes the launch that consumes it).
+uint32_t count_tiles(const uint64_t* dst, uint64_t p, uint64_t new_rows) {
+  uint32_t nt = 0;
+  uint64_t prev = UINT64_MAX;
+  for (uint64_t i = 0; i < p; ++i)
+    if (dst[i] / 32 != prev) prev = dst[i] / 32, ++nt;
+  if (new_rows && (new_rows - 1) / 32 != prev) ++nt;
+  return nt;
+}
+
+}  // namespace
+
+int delete_rows(DevEngine* eng, const char* coll, uint64_t n, const uint64_t* rows,
+                uint64_t* moved_from, uint64_t* moved_to, uint64_t* n_moved) {
+  if (!eng) return fail(VS_ERR_INVALID_ARG, "engine is NULL");
+  if (n_moved) *n_moved = 0;
+  auto c = find_coll(eng, coll);
+  if (!c) return fail(VS_ERR_NOT_FOUND, std::string("collection ") + (coll ? coll : "") +
+                                            " not found");
+  if (n == 0) return VS_OK;
+  if (!rows || !moved_from || !moved_to || !n_moved)
+    return fail(VS_ERR_INVALID_ARG, "rows, moved_from, moved_to and n_moved are required");
+  std::unique_lock<std::shared_mutex> wl(c->mu);
+  const uint64_t N = c->rows;
+  for (uint64_t i = 0; i < n; ++i)
+    if (rows[i] >= N)
+      return fail(VS_ERR_INVALID_ARG, "delete: row " + std::to_string(rows[i]) +
+                                          " is past the collection's " + std::to_string(N) + " rows");
+  // The counts the launches are sized by come from a sorted copy here (every
+  // row is read for the check above anyway); the lists themselves are built on
+  // the device, whose own counts are checked against these at the end.
+  std::vector<uint64_t> uniq(rows, rows + n);
+  std::sort(uniq.begin(), uniq.end());
+  uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+  const uint64_t m = uniq.size(), Nn = N - m;
+  const uint64_t p = (uint64_t)(std::lower_bound(uniq.begin(), uniq.end(), Nn) - uniq.begin());
+  const bool keep = c->q8 && q8_wanted_at(eng, *c, Nn);  // the int8 copy outlives the delete
+  const uint32_t nt = keep ? count_tiles(uniq.data(), p, Nn) : 0;
+
+  std::lock_guard<std::mutex> g(eng->work_mu);
+  VS_HIP(set_dev(eng), "hipSetDevice");
+  VS_HIP(use_stream(eng, eng->own), "stream order");
+  const uint32_t n32 = (uint32_t)N, nn32 = (uint32_t)Nn, ntiles_all = (nn32 + 31) / 32;
+  const size_t words = (N + 63) / 64, twords = (size_t)(ntiles_all + 63) / 64;
+  Carve cv;
+  const size_t o_zero = cv.take(32 + (words + twords) * 8);  // hdr[4], bits, tbits: one memset
+  const size_t zero_bytes = cv.off;
+  const size_t o_rows = cv.take(n * 8), o_to = cv.take(p * 8 + 8), o_from = cv.take(p * 8 + 8);
+  const size_t o_tiles = cv.take((size_t)nt * 4 + 4);
+  const size_t o_s0 = cv.take((size_t)vsk::compact_range_scratch_words(0, nn32) * 4);
+  const size_t o_s1 = cv.take((size_t)vsk::compact_range_scratch_words(nn32, n32) * 4);
+  const size_t o_s2 = cv.take((size_t)vsk::compact_range_scratch_words(0, ntiles_all) * 4);
+  if (eng->del.bytes < cv.off) {
+    VS_HIP(hipStreamSynchronize(eng->stream), "sync");
+    VS_HIP(eng->del.ensure(cv.off), "alloc delete scratch");
+  }
+  char* base = eng->del.as<char>();
+  uint64_t* hdr = (uint64_t*)(base + o_zero);  // [0] holes, [1] survivors, [2] tiles
+  uint64_t* bits = hdr + 4;
+  uint64_t* tbits = bits + words;
+  uint64_t* d_rows = (uint64_t*)(base + o_rows);
+  uint64_t* d_to = (uint64_t*)(base + o_to);
+  uint64_t* d_from = (uint64_t*)(base + o_from);
+  uint32_t* d_tiles = (uint32_t*)(base + o_tiles);
+  hipStream_t st = eng->stream;
+  // plan: the deleted rows' bitmap, then the holes below the new count and the
+  // surviving rows at or above it, both ascending
+  VS_HIP(hipMemsetAsync(base + o_zero, 0, zero_bytes, st), "zero delete bitmap");
+  VS_HIP(hipMemcpyAsync(d_rows, rows, n * 8, hipMemcpyHostToDevice, st), "delete rows H2D");
+  VS_HIP(vsk::launch_delete_mark(d_rows, n, n32, bits, st), "delete bitmap");
+  VS_HIP(vsk::launch_compact_range(bits, 0, nn32, false, d_to, nullptr, (uint32_t*)(base + o_s0),
+                                   hdr + 0, st),
+         "delete holes");
+  VS_HIP(vsk::launch_compact_range(bits, nn32, n32, true, d_from, nullptr,
+                                   (uint32_t*)(base + o_s1), hdr + 1, st),
+         "delete survivors");
+  // move: in place (sources >= Nn > destinations; vs_delete.hip move_rows_kernel)
+  VS_HIP(vsk::launch_move_rows(c->data, d_from, c->data, d_to, (uint32_t)c->row_bytes(),
+                               (uint32_t)p, st),
+         "delete move");
+  // The move is enqueued: from here nothing returns before the count is
+  // lowered and the copy and the filters are dealt with (delete_finish).
+  hipError_t te = hipSuccess;
+  if (keep) {
+    te = vsk::launch_mark_tiles(d_to, (uint32_t)p, nn32, tbits, st);
+    if (te == hipSuccess)
+      te = vsk::launch_compact_range(tbits, 0, ntiles_all, false, nullptr, d_tiles,
+                                     (uint32_t*)(base + o_s2), hdr + 2, st);
+  }
+  delete_finish(eng, *c, Nn, keep, te, d_tiles, nt);
+  uint64_t h[3] = {0, 0, 0};
+  hipError_t e = hipSuccess;
+  if (p) {
+    e = hipMemcpyAsync(moved_from, d_from, p * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(moved_to, d_to, p * 8, hipMemcpyDeviceToHost, st);
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(h, hdr, sizeof(h), hipMemcpyDeviceToHost, st);
+  const hipError_t se = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = se;
+  if (eng->del.bytes > kDelKeepBytes) eng->del.release();
+  if (e != hipSuccess) return fail_after_compaction(e, "delete: reading the moved pairs back");
+  if (c->q8 && h[2] != nt) c->q8_free();  // requantised from another list than the host sized
+  if (h[0] != p || h[1] != p)
+    return fail(VS_ERR_INTERNAL, "delete: the device's plan (" + std::to_string(h[0]) + " holes, " +
+                                     std::to_string(h[1]) + " survivors) differs from the host's (" +
+                                     std::to_string(p) + "); the rows were already compacted, so "
+                                     "the caller's ids no longer match this collection's rows: "
+                                     "drop or restore it");
+  *n_moved = p;
+  return VS_OK;
+}
+
+int delete_apply(DevEngine* eng, const char* coll, uint64_t new_rows, uint64_t n,
+                 const uint64_t* dst_rows, const void* raw) {
+  if (!eng) return fail(VS_ERR_INVALID_ARG, "engine is NULL");
+  auto c = find_coll(eng, coll);
+  if (!c) return fail(VS_ERR_NOT_FOUND, std::string("collection ") + (coll ? coll : "") +
+                                            " not found");
+  if (n && (!dst_rows || !raw)) return fail(VS_ERR_INVALID_ARG, "dst_rows and raw are required");
+  std::unique_lock<std::shared_mutex> wl(c->mu);
+  if (new_rows > c->rows) return fail(VS_ERR_INVALID_ARG, "delete: new row count past the rows");
+  std::vector<uint64_t> sorted(dst_rows, dst_rows + n);
+  std::sort(sorted.begin(), sorted.end());
+  for (uint64_t i = 0; i < n; ++i)
+    if (sorted[i] >= new_rows || (i && sorted[i] == sorted[i - 1]))
+      return fail(VS_ERR_INVALID_ARG, "delete: destination rows must be distinct and below the "
+                                      "new row count");
+  const bool keep = c->q8 && q8_wanted_at(eng, *c, new_rows);
+  const uint32_t nt = keep ? count_tiles(sorted.data(), n, new_rows) : 0;
+  std::lock_guard<std::mutex> g(eng->work_mu);
+  VS_HIP(set_dev(eng), "hipSetDevice");
+  VS_HIP(use_stream(eng, eng->own), "stream order");
+  const uint32_t nn32 = (uint32_t)new_rows, ntiles_all = (nn32 + 31) / 32;
+  const size_t twords = (size_t)(ntiles_all + 63) / 64, rb = c->row_bytes();
+  Carve cv;
+  const size_t o_zero = cv.take(32 + twords * 8);  // hdr[4], tbits
+  const size_t zero_bytes = cv.off;
+  const size_t o_to = cv.take(n * 8 + 8), o_raw = cv.take(n * rb + 16);
+  const size_t o_tiles = cv.take((size_t)nt * 4 + 4);
+  const size_t o_s2 = cv.take((size_t)vsk::compact_range_scratch_words(0, ntiles_all) * 4);
+  if (eng->del.bytes < cv.off) {
+    VS_HIP(hipStreamSynchronize(eng->stream), "sync");
+    VS_HIP(eng->del.ensure(cv.off), "alloc delete scratch");
+  }
+  char* base = eng->del.as<char>();
+  uint64_t* hdr = (uint64_t*)(base + o_zero);
+  uint64_t* tbits = hdr + 4;
+  uint64_t* d_to = (uint64_t*)(base + o_to);
+  uint32_t* d_tiles = (uint32_t*)(base + o_tiles);
+  hipStream_t st = eng->stream;
+  VS_HIP(hipMemsetAsync(base + o_zero, 0, zero_bytes, st), "zero delete bitmap");
+  if (n) {
+    VS_HIP(hipMemcpyAsync(d_to, dst_rows, n * 8, hipMemcpyHostToDevice, st), "delete rows H2D");
+    VS_HIP(hipMemcpyAsync(base + o_raw, raw, n * rb, hipMemcpyHostToDevice, st), "delete rows H2D");
+    VS_HIP(vsk::launch_move_rows(base + o_raw, nullptr, c->data, d_to, (uint32_t)rb, (uint32_t)n,
+                                 st),
+           "delete move");
+  }
+  hipError_t te = hipSuccess;  // as delete_rows: no return before delete_finish
+  if (keep) {
+    te = vsk::launch_mark_tiles(d_to, (uint32_t)n, nn32, tbits, st);
+    if (te == hipSuccess)
+      te = vsk::launch_compact_range(tbits, 0, ntiles_all, false, nullptr, d_tiles,
+                                     (uint32_t*)(base + o_s2), hdr + 2, st);
+  }
+  delete_finish(eng, *c, new_rows, keep, te, d_tiles, nt);
+  uint64_t h[3] = {0, 0, 0};
+  hipError_t e = hipMemcpyAsync(h, hdr, sizeof(h), hipMemcpyDeviceToHost, st);
+  const hipError_t se = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = se;
+  if (eng->del.bytes > kDelKeepBytes) eng->del.release();
+  if (e != hipSuccess) return fail_after_compaction(e, "delete: shard sync");
+  if (c->q8 && h[2] != nt) c->q8_free();
   return VS_OK;
 }
 

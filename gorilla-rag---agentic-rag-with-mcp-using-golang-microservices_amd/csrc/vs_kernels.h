@@ -440,6 +440,33 @@ hipError_t launch_checksum_rows(const void* p, uint64_t rows, uint32_t row_bytes
 hipError_t launch_remap_keys(uint64_t* keys, uint64_t n, uint32_t stride, uint32_t offset,
                              uint32_t base, hipStream_t st);
 
+// Point deletion (vs_delete.hip; include/vsearch.h vs_delete). All on `st`.
+// Bit r of bits[r / 64] |= 1 for every rows[i] (< n_rows; others are skipped):
+// repeats count once. bits: ceil(n_rows / 64) words, zeroed by the caller.
+hipError_t launch_delete_mark(const uint64_t* rows, uint64_t n, uint32_t n_rows, uint64_t* bits,
+                              hipStream_t st);
+// launch_compact_rows over a bit range: the numbers b in [lo, hi) whose bit is
+// set (clear, with `invert`), ascending, as 64-bit (out64) or 32-bit (out32)
+// values -- exactly one of the two -- and their count in *total. scratch:
+// compact_range_scratch_words(lo, hi) u32.
+uint32_t compact_range_scratch_words(uint32_t lo, uint32_t hi);
+hipError_t launch_compact_range(const uint64_t* bits, uint32_t lo, uint32_t hi, bool invert,
+                                uint64_t* out64, uint32_t* out32, uint32_t* scratch,
+                                uint64_t* total, hipStream_t st);
+// Row src_rows[i] of src (row i when src_rows is null) -> row dst_rows[i] of
+// dst for i < n_pairs, bytes as stored; one wave per pair, 16-byte accesses
+// when row_bytes and both buffers allow, else 4- or 2-byte ones (row_bytes is
+// even). src == dst is allowed when no row is both a source and a destination.
+hipError_t launch_move_rows(const void* src, const uint64_t* src_rows, void* dst,
+                            const uint64_t* dst_rows, uint32_t row_bytes, uint32_t n_pairs,
+                            hipStream_t st);
+// Bit t of tbits (zeroed by the caller, ceil(ceil(n_rows / 32) / 64) words) for
+// the 32-row tile of every dst_rows[i] and for the tile of row n_rows - 1:
+// launch_compact_range(tbits, 0, ceil(n_rows / 32), ..., out32) then gives the
+// de-duplicated tile list launch_q8_quantize takes.
+hipError_t launch_mark_tiles(const uint64_t* dst_rows, uint32_t n_pairs, uint32_t n_rows,
+                             uint64_t* tbits, hipStream_t st);
+
 int device_cu_count();
 
 }  // namespace vsk

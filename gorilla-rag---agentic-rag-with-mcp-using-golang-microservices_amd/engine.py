@@ -52,7 +52,7 @@ EXPORTS = (
     "vs_filter_create", "vs_filter_drop", "vs_search_filter_id", "vs_open_multi",
     "vs_engine_layout", "vs_comm_unique_id", "vs_comm_init", "vs_gather_merge_keys",
     "vs_copy_last_error", "vs_build_id", "vs_collection_placement", "vs_runtime_check",
-    "vs_collection_prefilter_bytes", "vs_collection_spec_stats",
+    "vs_collection_prefilter_bytes", "vs_collection_spec_stats", "vs_delete",
 )
 COMM_ID_BYTES = 128
 
@@ -132,6 +132,7 @@ def load_library(path: str = LIB_PATH):
         "vs_collection_info": ([vp, cp, vp, vp, vp, vp], i32),
         "vs_collection_drop": ([vp, cp], i32),
         "vs_upsert": ([vp, cp, u64, u32, vp, vp], i32),
+        "vs_delete": ([vp, cp, u64, vp, vp, vp, vp], i32),
         "vs_generate": ([vp, cp, u64, u64], i32),
         "vs_generate_vectors": ([vp, u64, u64, u64, u32, vp, vp], i32),
         "vs_read_rows": ([vp, cp, u64, u64, vp], i32),
@@ -318,6 +319,19 @@ class VectorEngine:
         if v.ndim != 2 or v.shape[0] != r.shape[0]:
             raise ValueError("vectors must be (n, dim) with one row number per vector")
         _check(self._L.vs_upsert(self._h, name.encode(), r.shape[0], v.shape[1], _p(r), _p(v)))
+
+    def delete(self, name: str, rows: Sequence[int]) -> Tuple[np.ndarray, np.ndarray]:
+        """vs_delete: removes `rows` (repeats count once) by compaction and
+        returns (moved_from, moved_to): the stored row moved_from[i] is now row
+        moved_to[i], and the collection holds rows - len(set(rows)) rows. The
+        caller renumbers its ids and payloads from the pairs."""
+        r = np.ascontiguousarray(rows, np.uint64).ravel()
+        frm = np.zeros(max(r.size, 1), np.uint64)
+        to = np.zeros(max(r.size, 1), np.uint64)
+        nm = ctypes.c_uint64()
+        _check(self._L.vs_delete(self._h, name.encode(), r.size, _p(r), _p(frm), _p(to),
+                                 ctypes.byref(nm)))
+        return frm[:nm.value].copy(), to[:nm.value].copy()
 
     def generate(self, name: str, n: int, seed: int):
         _check(self._L.vs_generate(self._h, name.encode(), n, seed))

@@ -87,7 +87,8 @@ def validate(path: str, body: bytes) -> Tuple[int, str]:
 
 
 class VectorService:
-    """rag/vector-service's four handlers over an engine (not owned)."""
+    """rag/vector-service's four handlers, and the /delete extension, over an
+    engine (not owned)."""
 
     def __init__(self, engine, config: Optional[dict] = None):
         L = load_service_library()
@@ -120,6 +121,16 @@ class VectorService:
         if rc != 0:
             raise VSError(rc, "vsvc_handle failed")
         return st.value, _take(self._L, out, n.value), ct.value.decode()
+
+    def delete(self, collection: str, ids=None, filter=None) -> Tuple[int, bytes, str]:
+        """POST /delete (an extension, include/vsearch_service.h): the points
+        with these `ids`, or those whose payload matches `filter`."""
+        body = {"collection": collection}
+        if ids is not None:
+            body["ids"] = list(ids)
+        if filter is not None:
+            body["filter"] = filter
+        return self.handle("POST", "/delete", json.dumps(body).encode())
 
     def bulk_generate(self, collection: str, n: int, seed: int) -> None:
         """n synthetic device-generated points with synthetic UUIDs (empty collection)."""

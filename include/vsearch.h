@@ -14,6 +14,10 @@
  * The gRPC client globals they go through (main.go:44-51, created at
  * main.go:56-65) are replaced by one engine handle from vs_open.
  *
+ * Points.Delete has no call site in the reference (its ingest mints fresh
+ * UUIDs and nothing removes a point); vs_delete exists for callers that need
+ * it, as the service's POST /delete extension does.
+ *
  * Conventions
  *  - Plain C types only: no HIP, torch or Go types in any signature.
  *  - Every function returns VS_OK (0) or a negative vs_status. The message of
@@ -203,6 +207,44 @@ int vs_collection_spec_stats(vs_engine* eng, const char* name, uint64_t out[4]);
  * Returns after the data is resident. */
 int vs_upsert(vs_engine* eng, const char* coll, uint64_t n, uint32_t dim,
               const uint64_t* rows, const float* vecs);
+
+/* Point deletion (Qdrant's Points.Delete; no call site in the reference).
+ * Deletion COMPACTS: surviving tail rows move into the holes and the
+ * collection is truncated, so rows [0, rows) stay dense and live and every
+ * search path, the int8 prefilter, snapshots and the striped layout keep
+ * their contracts (a tombstone mask would switch the fast paths off).
+ *
+ * `rows` are collection rows as vs_upsert takes them (global rows of a
+ * row-striped collection); repeats count once. With N the row count, S the
+ * distinct rows given, m = |S| and N' = N - m:
+ *   holes      H = ascending { s in S : s < N' }
+ *   survivors  T = ascending { r in [N', N) : r not in S }      (|H| = |T|)
+ * The stored bits (fp32 or bf16, exactly as stored: nothing is preprocessed
+ * again) of row T[i] move to row H[i] for every i, and the row count becomes
+ * N'. moved_from[i] = T[i], moved_to[i] = H[i], *n_moved = |H|; the caller's
+ * two arrays hold at least `n` entries. The caller owns ids and payloads and
+ * renumbers them from these pairs, as vs_upsert leaves ids to the caller. Tie
+ * order stays (score desc, row asc) on the new numbers.
+ *  - n == 0 is a no-op returning VS_OK. Any row >= N: VS_ERR_INVALID_ARG and
+ *    nothing changes. Deleting every row leaves an empty collection that can
+ *    be appended to again.
+ *  - Capacity is kept (no HBM is returned); vs_upsert's append rule then
+ *    applies to the new count: appends must form [N', N' + j).
+ *  - A delete is a write: it waits for searches in flight, as vs_upsert does,
+ *    and returns after the data is resident.
+ *  - Device filters (vs_filter_create) of the collection are dropped: their
+ *    bits name old row numbers. vs_search_filter_id with such an id fails from
+ *    then on, also after appends bring the row count back.
+ *  - The int8 prefilter copy stays in step (only the tiles that received a
+ *    row, and the one holding the new last row, are requantised); a collection
+ *    that shrinks under the size that keeps a copy loses it, and gets a new one
+ *    when it grows back.
+ *  - A device failure once the rows have moved (VS_ERR_DEVICE / VS_ERR_INTERNAL
+ *    whose message says so) leaves the collection compacted and searchable,
+ *    but the pairs are lost: the caller's ids no longer match its rows, and
+ *    the collection should be dropped or restored. */
+int vs_delete(vs_engine* eng, const char* coll, uint64_t n, const uint64_t* rows,
+              uint64_t* moved_from, uint64_t* moved_to, uint64_t* n_moved);
 
 /* Appends `n` synthetic unit-norm rows generated on the device by the
  * counter-based generator of DESIGN.md §4 (seed, global row numbers

@@ -14,6 +14,27 @@
  * served in-process by vsvc_handle, or over TCP by vsvc_http_start (the
  * reference's http.ListenAndServe, main.go:75-77).
  *
+ * One route is an extension, outside the reference's four:
+ *
+ *   POST /delete       (no reference handler; Qdrant's Points.Delete)
+ *
+ * Body {"collection":"..","ids":["uuid",..]} or {"collection":"..",
+ * "filter":{..}}: exactly one of `ids` / `filter`, else 400; an empty
+ * `filter` object (it would match every point) is 400 too. `filter` is the
+ * payload-equality matcher of "filter":"match" (below), whatever the service's
+ * filter setting -- {"document_id":".."} removes a document's chunks. Unknown
+ * ids are ignored, as Qdrant ignores them; an unparsable UUID is answered as
+ * /upsert answers it. Reply {"collection","deleted":n,"status":"success"},
+ * encoded like /upsert's. The points go through vs_delete (include/vsearch.h
+ * states the compaction rule) and the ids and payloads of the moved rows are
+ * renumbered under the collection's writer lock, so a /search answer belongs
+ * to one version; a deleted id upserted again is a new point. 400 for a
+ * collection holding bulk-generated points (vsvc_bulk_generate: no per-row
+ * state to renumber); 501 when the engine library has no vs_delete (the
+ * symbol is referenced weakly). If the engine fails after it compacted the
+ * rows (its pairs are then lost), the collection is emptied on both sides and
+ * the 500 says so: its ids could no longer be matched to rows.
+ *
  * Point UUIDs and payloads live here (a UUID -> row map and a row-indexed
  * payload store per collection); the engine sees dense rows only. A Go
  * deployment binds the same engine C-ABI through cgo and
@@ -129,7 +150,7 @@ void vsvc_free(char* p);
  * interface{} (sorted keys, shortest floats, HTML escaping, trailing '\n').
  * Returns 0, or -1 with *out = the syntax error text. */
 int vsvc_reencode(const char* json, size_t len, char** out);
-/* Validates a /search or /upsert body exactly as the handler's decode step
+/* Validates a /search, /upsert or /delete body exactly as the handler's decode step
  * does, without touching the engine. Returns the HTTP status the handler
  * would answer for a malformed body (400) or 0 when the body decodes;
  * *msg (malloc'd) gets the error text or "". */
