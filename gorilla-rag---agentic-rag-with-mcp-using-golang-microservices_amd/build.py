@@ -32,6 +32,9 @@ ROOT = os.path.dirname(HERE)
 # but no part of them: not in tree_files(), so not in the build id
 KPROBE_SRC = os.path.join(ROOT, "tests", "kprobe", "vs_kprobe.cpp")
 KPROBE_LIB = os.path.join(HERE, "lib", "libvs_kprobe.so")
+# the int8 pass with its run_if word (tests/test_q8_split_wg_gpu.py), a shim of its own
+KPROBE_RUNIF_SRC = os.path.join(ROOT, "tests", "kprobe", "vs_kprobe_runif.cpp")
+KPROBE_RUNIF_LIB = os.path.join(HERE, "lib", "libvs_kprobe_runif.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("VS_OFFLOAD_ARCH", "gfx950")
 
@@ -145,6 +148,11 @@ def build(verbose: bool = False, force: bool = False) -> str:
                "-o", KPROBE_LIB, "-L" + os.path.dirname(LIB), "-lvsearch", "-Wl,-rpath,$ORIGIN",
                "-Wl,-soname,libvs_kprobe.so"]
         _run_if_changed(KPROBE_LIB, [KPROBE_SRC, LIB] + hdrs, cmd, verbose, force)
+    if os.path.exists(KPROBE_RUNIF_SRC):
+        cmd = [HIPCC, "-std=c++17", "-fPIC", "-O2", "-Wall", "-shared", "-I" + CSRC, KPROBE_RUNIF_SRC,
+               "-o", KPROBE_RUNIF_LIB, "-L" + os.path.dirname(LIB), "-lvsearch", "-Wl,-rpath,$ORIGIN",
+               "-Wl,-soname,libvs_kprobe_runif.so"]
+        _run_if_changed(KPROBE_RUNIF_LIB, [KPROBE_RUNIF_SRC, LIB] + hdrs, cmd, verbose, force)
     return LIB
 
 

@@ -1590,9 +1590,22 @@ hipError_t launch_compact_rows(const uint64_t* allow, uint32_t n_rows, uint32_t*
 // 256-register budget); G = 4 (ablation) -> 4 waves of 64 queries (one per
 // SIMD, 512-register budget), which halves the LDS reads per MFMA. The int8
 // pass at G = 2 (768-d) halves them at two waves per SIMD instead: 64 queries
-// x 16 rows a wave (the query-half mapping, kQH in the kernel).
+// x 16 rows a wave (the query-half mapping, kQH in the kernel). The two wave
+// parities of that mapping share nothing, so the library launches them as two
+// 4-wave workgroups per CU (kMfVarSplit below): the two waves of a SIMD then
+// wait at different barriers and drift out of phase, one's epilogue, barrier
+// wait and DMA issue under the other's MFMAs.
 constexpr int kMfG = 2;
 constexpr int mf_waves(int g) { return g == 4 ? 4 : 8; }
+// VAR bit of the split-workgroup instance of the two-group int8 pass: the
+// eight logical waves run as two 4-wave workgroups (one per wave parity), two
+// workgroups a CU, one wave of each a SIMD (kSplit in the kernel)
+constexpr int kMfVarSplit = 268435456;
+constexpr int mf_waves_var(int g, int var) { return (var & kMfVarSplit) ? 4 : mf_waves(g); }
+// waves per SIMD the register budget is sized for (__launch_bounds__)
+constexpr int mf_waves_per_simd(int g, int var) {
+  return (var & kMfVarSplit) ? 2 : (mf_waves(g) == 4 ? 1 : 8 / mf_waves(g));
+}
 // query groups per wave from the row bytes: the B fragments of a wave's
 // queries take G * rby / 16 VGPRs, <= 192 (bf16 D <= 768 and fp32 D <= 384:
 // G = 2; bf16 D = 1024 / 1536 and fp32 D = 512 / 768: G = 1)
@@ -1843,8 +1856,10 @@ struct MfFull {
 // Byte geometry of the streamed rows (EB = element bytes: 2 bf16, 4 fp32).
 // A step is 64 bytes of a row: 32 k of bf16 (one 16x16x32 MFMA per row half
 // and query group) or 16 k of fp32 (four 16x16x4 MFMAs).
+// RG: the 8-row groups of a 32-row tile that one workgroup streams (4; the
+// split-workgroup int8 pass streams its parity's 2).
 template <int D, int RING = kMfRingBytes, int TAIL = kMfListBytes, int WAVES = 8, int CSX = 0,
-          int EB = 2>
+          int EB = 2, int RG = 4>
 struct MfShape {
   static constexpr int RBY = D * EB;                      // bytes per row
   static constexpr int T = RBY / 64;                      // 64-B MFMA steps per row
@@ -1852,9 +1867,10 @@ struct MfShape {
   static constexpr int CS4 = CSX ? CSX : ((RBY % 512 == 0) ? 4 : 2);
   static constexpr int CT = CS4 * 2;                      // steps per chunk
   static constexpr int CPT = RBY / (128 * CS4);           // chunks per 32-row tile
-  static constexpr int PIECES = CS4 * 4;                  // 1 KiB LDS-DMA pieces per chunk
+  static constexpr int PIECES = CS4 * RG;                 // 1 KiB LDS-DMA pieces per chunk
   static constexpr int PPW = PIECES / WAVES;              // pieces per wave per chunk
-  static constexpr int CHUNK_BYTES = PIECES * 1024;       // 32 rows x CS4*128 B
+  static constexpr int CHUNK_BYTES = PIECES * 1024;       // 8 RG rows x CS4*128 B
+  static constexpr int STEP2_BYTES = RG * 1024;           // the RG pieces of two steps (128 B a row)
   static constexpr int NSLOT = RING / CHUNK_BYTES;
   static constexpr int AHEAD = NSLOT - 1;                 // chunks in flight
   static constexpr int LDS_BYTES = NSLOT * CHUNK_BYTES + TAIL;  // ring + lists / counters
@@ -1873,12 +1889,18 @@ struct MfShape {
 // only (never keeps a row). Every mode that streams streams as the product.
 // VAR (a bit set; any other bit fails to compile): 256 = a 144 KiB ring
 // (not MODE 8, whose lists need the room), 2048 = 24 KiB K-chunks (D = 768);
-// the library runs 0 or 256 + 2048 (mf_product_var, launch_mfma_cand_q8).
+// the library runs 0 or 256 + 2048 (mf_product_var), and 256 + 2048 +
+// 268435456 for the 768-d int8 pass (launch_mfma_cand_q8).
 // Tools only: 8192 = per-workgroup clocks into a.lists, 16777216 = the int8
 // pass never appends (a timing arm: wrong answers), 4096 = the two-group int8
 // pass on the row-major mapping (32 queries x 32 rows a wave) that the
 // query-half mapping below replaced: the same bytes out, twice the LDS
-// reads. The experiments that
+// reads; 268435456 (kMfVarSplit) = the two-group int8 pass as two 4-wave
+// workgroups per logical workgroup, launched on twice the blocks of 256
+// threads: physical block b is logical workgroup b >> 1 with wave parity
+// p = b & 1, its wave lw logical wave 2 lw + p; each has its own barrier and
+// its own 72 KiB ring of its parity's half of every tile; the same bytes
+// out. With 8192 it also records every wave's hardware id. The experiments that
 // were measured and taken out of this kernel are listed in DESIGN.md
 // ("Experiments removed from the MFMA scan").
 // F32: fp32 rows and queries on v_mfma_f32_16x16x4_f32 (exact f32 products,
@@ -1890,21 +1912,28 @@ constexpr bool mf_mode_known(int mode) {
          mode == 6;
 }
 constexpr bool mf_var_known(int var) {
-  return (var & ~(256 | 2048 | 4096 | 8192 | 16777216)) == 0;
+  return (var & ~(256 | 2048 | 4096 | 8192 | 16777216 | kMfVarSplit)) == 0;
 }
 
 template <int D, int MODE = 0, int VAR = 0, int G = mf_groups(D), bool F32 = false, bool I8 = false>
-__global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_waves(G)) void mfma_topk_kernel(
+__global__ __launch_bounds__(64 * mf_waves_var(G, VAR), mf_waves_per_simd(G, VAR)) void mfma_topk_kernel(
     const MfArgs a) {
   static_assert(mf_mode_known(MODE), "MODE: 0, 3, 8 (product) or 1, 2, 4, 5, 6 (decomposition)");
-  static_assert(mf_var_known(VAR), "VAR: only bits 256, 2048, 4096, 8192 and 16777216 exist");
-  constexpr int WAVES = mf_waves(G), THREADS = 64 * WAVES, QPW = 16 * G;
+  static_assert(mf_var_known(VAR),
+                "VAR: only bits 256, 2048, 4096, 8192, 16777216 and 268435456 exist");
+  // WAVES: the waves of a (physical) workgroup; LWAVES: those of the logical
+  // workgroup, which the piece, query and slab ownership is written in
+  constexpr bool kSplit = (VAR & kMfVarSplit) != 0;
+  static_assert(!kSplit || (I8 && G == 2 && D == 768 && (VAR & (4096 | 2048 | 256)) == (2048 | 256)),
+                "split workgroups: the query-half 768-d int8 pass on whole-row chunks");
+  constexpr int WAVES = mf_waves_var(G, VAR), THREADS = 64 * WAVES, QPW = 16 * G;
+  constexpr int LWAVES = kSplit ? 2 * WAVES : WAVES;
   constexpr int EB = F32 ? 4 : (I8 ? 1 : 2);
-  static_assert(!I8 || (!F32 && (MODE == 0 || MODE == 1 || MODE == 4 || MODE == 6)),
+  static_assert(!I8 || (!F32 && (MODE == 0 || MODE == 1 || MODE == 2 || MODE == 4 || MODE == 6)),
                 "int8: the main pass only");
   if (a.run_if && *a.run_if == 0u) return;  // uniform: the whole launch stands down
   constexpr int RBY = D * EB;
-  static_assert(WAVES * QPW <= (int)kMfmaQueries, "one launch covers <= kMfmaQueries");
+  static_assert(LWAVES * QPW <= (int)kMfmaQueries, "one launch covers <= kMfmaQueries");
   // Query-half mapping of the two-group int8 pass (768-d). Waves 2j and 2j+1
   // both hold queries 64j .. 64j+63 (GB = 4 B groups: 192 VGPRs, the bf16
   // 768-d pass's budget) and wave parity p takes 16 of a tile's 32 rows as its
@@ -1944,8 +1973,11 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
   static_assert(kStageCap <= 64, "one flush: a lane per record");
   static_assert(!kStage || !kBigRing || 144 * 1024 + 16 + kStageBytes <= 160 * 1024,
                 "staging area: what the 144 KiB ring leaves of the LDS");
-  using S = MfShape<D, kBigRing ? 144 * 1024 : kMfRingBytes,
-                    MODE == 8 ? kMfListBytes : 16 + kCntBytes + kStageBytes, WAVES, kCsx, EB>;
+  // split workgroups: each streams its parity's two row groups, half of every
+  // chunk, through half the ring (the same slots and bytes in flight a CU)
+  using S = MfShape<D, (kBigRing ? 144 * 1024 : kMfRingBytes) / (kSplit ? 2 : 1),
+                    MODE == 8 ? kMfListBytes : 16 + kCntBytes + kStageBytes, WAVES, kCsx, EB,
+                    kSplit ? 2 : 4>;
   constexpr bool kDma = MODE != 4 && MODE != 5;  // decomposition arms without the stream
   constexpr bool kLists = MODE == 8;
   constexpr int PPW = S::PPW;
@@ -1965,15 +1997,22 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
   lds_vu32_t* cntl = (lds_vu32_t*)(lds_ptr_t)(smem + S::NSLOT * S::CHUNK_BYTES + 16);
 
   const int lane = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  // w, bid, nbl: the logical wave, workgroup and workgroup count. Split
+  // workgroups: blocks 2j and 2j + 1 are the parities p = 0 / 1 of logical
+  // workgroup j, wave lw of a block its logical wave 2 lw + p; everything
+  // below (rows, queries, pieces, slabs, counts) is owned by logical index.
+  const int pw = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int w = kSplit ? 2 * pw + (int)(blockIdx.x & 1u) : pw;
+  const uint32_t bid = kSplit ? blockIdx.x >> 1 : blockIdx.x;
+  const uint32_t nbl = kSplit ? gridDim.x >> 1 : gridDim.x;
   const int col = lane & 15;  // MFMA column (query in group) / A-fragment row
   const int kq = lane >> 4;   // 8-element k slice; C rows 4kq .. 4kq+3
   const uint32_t k = a.k;
-  uint32_t wr0 = blockIdx.x * a.rows_per_wg;
+  uint32_t wr0 = bid * a.rows_per_wg;
   uint32_t wr1 = (uint64_t)wr0 + a.rows_per_wg < a.n_rows ? wr0 + a.rows_per_wg : a.n_rows;
   if (a.wg_tile) {  // a weighted split (per-XCD speeds)
-    wr0 = a.wg_tile[blockIdx.x] * 32u;
-    const uint64_t e = (uint64_t)a.wg_tile[blockIdx.x + 1] * 32u;
+    wr0 = a.wg_tile[bid] * 32u;
+    const uint64_t e = (uint64_t)a.wg_tile[bid + 1] * 32u;
     wr1 = e < a.n_rows ? (uint32_t)e : a.n_rows;
   }
   uint32_t ntiles = (wr1 - wr0 + 31) / 32;
@@ -2000,7 +2039,9 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
   uint32_t loff[PPW];
 #pragma unroll
   for (int i = 0; i < PPW; ++i) {
-    const int b = w + WAVES * i;
+    // (split workgroups: logical wave w's pieces are rg = w & 3, all of its
+    // own parity, so each block issues exactly its half of the chunk)
+    const int b = w + LWAVES * i;
     const int s4l = b >> 2, rg = b & 3;
     const int g_ri = lane >> 3, c16 = (lane & 7) ^ mf_swz(g_ri, rg);
     loff[i] = (uint32_t)((rg * 8 + g_ri) * RBY + s4l * 128 + c16 * 16);
@@ -2037,11 +2078,13 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
         (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)sp));
 #pragma unroll
     for (int i = 0; i < PPW; ++i) {
-      const int b = w + WAVES * i;
+      const int b = w + LWAVES * i;
       const int s4l = b >> 2, rg = b & 3;
+      // piece (s4l, rg) of the slot; split workgroups keep rg >> 1 of their two
+      const int pc = kSplit ? s4l * 2 + (rg >> 1) : s4l * 4 + rg;
       glds16<kNtDma>(src, loff[i],
                      (uint32_t)__builtin_amdgcn_readfirstlane(
-                         (int)(lds_base + snext + (uint32_t)((s4l * 4 + rg) * 1024))));
+                         (int)(lds_base + snext + (uint32_t)(pc * 1024))));
     }
     advance();
   };
@@ -2088,7 +2131,7 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
     if constexpr (kRegCnt) {
       cnt_r[g] = 0u;
       if constexpr (!kQH)
-        slot0[g] = (uint32_t)(((size_t)blockIdx.x * kMfmaQueries + ql[g]) * a.cand_cap +
+        slot0[g] = (uint32_t)(((size_t)bid * kMfmaQueries + ql[g]) * a.cand_cap +
                               (uint32_t)kq * (a.cand_cap >> 2));
     }
     qvalid[g] = ql[g] < a.nq_valid;
@@ -2123,10 +2166,14 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
     const int rg = rr >> 3, ri = rr & 7, sw = mf_swz(ri, rg);
 #pragma unroll
     for (int tt = 0; tt < 2; ++tt)
-      off[hr][tt] = rg * 1024 + ri * 128 + (((kQH ? qh_chunk(tt) : 4 * tt + kq) ^ sw) << 4);
+      // (split workgroups: the slot holds pieces rg >> 1 = 0 / 1 of this
+      // parity; the swizzle keeps the real rg, so the bank groups are the same)
+      off[hr][tt] = (kSplit ? rg >> 1 : rg) * 1024 + ri * 128 +
+                    (((kQH ? qh_chunk(tt) : 4 * tt + kq) ^ sw) << 4);
   }
   auto lds_a = [&](const unsigned char* sb, int s, int hr) -> bf16x8_t {
-    return __builtin_bit_cast(bf16x8_t, *(const uint4*)(sb + (s >> 1) * 4096 + off[hr][s & 1]));
+    return __builtin_bit_cast(
+        bf16x8_t, *(const uint4*)(sb + (s >> 1) * S::STEP2_BYTES + off[hr][s & 1]));
   };
 
   // The query fragments and bounds are loads the compiler's waitcnt pass
@@ -2303,7 +2350,9 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
     if (!full) {  // padding / filtered rows -> INT_MIN in the slab, as q8_epi_mx
       uint32_t tid = threadIdx.x;
       asm volatile("" : "+v"(tid));  // opaque: nothing of this body in the full tiles
-      const uint32_t r0 = 16u * ((tid >> 5) & 1u) + 8u * ((tid >> 6) & 1u) + 4u * ((tid >> 4) & 1u);
+      // (the wave parity: of the logical wave)
+      const uint32_t par = kSplit ? (uint32_t)(w & 1) : (tid >> 6) & 1u;
+      const uint32_t r0 = 16u * ((tid >> 5) & 1u) + 8u * par + 4u * ((tid >> 4) & 1u);
       uint32_t amv = 0xFu;
       if (a.allow) amv = ((uint32_t)(a.allow[trow0 >> 6] >> (trow0 & 32)) >> r0) & 0xFu;
       const uint32_t rb = trow0 + r0;
@@ -2343,7 +2392,7 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
         if (cg < sub) {
           // uniform bases of this workgroup's slabs and tile words; the slot in
           // the workgroup is boff >> 5 (boff & 16: the upper half's lane)
-          const size_t wg0 = (size_t)blockIdx.x * kMfmaQueries * a.cand_cap;
+          const size_t wg0 = (size_t)bid * kMfmaQueries * a.cand_cap;
           const uint32_t boff = qh_boff + (((uint32_t)g * 16u * a.cand_cap + cg) << 5);
           *(f32x4_t*)((unsigned char*)((f32x4_t*)a.cand + 2 * wg0) + boff) = ac[0][g];
           if (kq < 2) (a.cand_tile + wg0)[boff >> 5] = a.row_base + trow0;
@@ -2601,7 +2650,7 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
     if constexpr (MODE == 0 && kQH) {
       // lanes kq and kq ^ 2 hold the same words of quarter 2p + (kq & 1) of query ql[g]
       if (kq < 2) {
-        const size_t ci = ((size_t)ql[g] * gridDim.x + blockIdx.x) * 4 + 2 * (w & 1) + kq;
+        const size_t ci = ((size_t)ql[g] * nbl + bid) * 4 + 2 * (w & 1) + kq;
         a.cand_cnt[ci] = cnt_r[g];
         if (a.cand_max) a.cand_max[ci] = (uint32_t)qmx_r[g];
       }
@@ -2627,7 +2676,22 @@ __global__ __launch_bounds__(64 * mf_waves(G), mf_waves(G) == 4 ? 1 : 8 / mf_wav
       }
     }
   }
-  if constexpr (kClock)
+  if constexpr (kClock && kSplit) {
+    // 8 words per physical block: the four clocks, then each wave's hardware
+    // id register (HW_ID: SIMD bits 5:4, CU 11:8, SH 12, SE 15:13) with the
+    // XCC id (register XCC_ID, bits 3:0) in the upper word
+    if (lane == 0) {
+      const uint32_t hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);
+      const uint32_t xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);
+      a.lists[8 * blockIdx.x + 4 + pw] = ((uint64_t)xcc << 32) | hw;
+    }
+    if (threadIdx.x == 0) {
+      a.lists[8 * blockIdx.x] = tclk0;
+      a.lists[8 * blockIdx.x + 1] = tclk1;
+      a.lists[8 * blockIdx.x + 2] = tclk2;
+      a.lists[8 * blockIdx.x + 3] = wall_clock64();
+    }
+  } else if constexpr (kClock)
     if (threadIdx.x == 0) {  // [start, prologue done, tiles done, end] per workgroup
       a.lists[4 * blockIdx.x] = tclk0;
       a.lists[4 * blockIdx.x + 1] = tclk1;
@@ -2773,7 +2837,8 @@ hipError_t launch_mfma_cand(const void* X, bool f32, uint32_t dim, uint32_t n_ro
 }
 
 // int8 prefilter pass (r04): D = 768 rows of int8 (768 B, whole-row 24 KiB
-// K-chunks through the 144 KiB ring), 256 queries; D = 1024 (C5's rows):
+// K-chunks through the 144 KiB ring, as two 4-wave workgroups per logical
+// workgroup with 72 KiB each: kMfVarSplit), 256 queries; D = 1024 (C5's rows):
 // 16 KiB chunks (32 rows x 512 B) through the 144 KiB ring, 128 queries per
 // launch as the bf16 pass and sample pass there. No filter.
 bool q8_supported(uint32_t dim, bool f32) {
@@ -2803,8 +2868,10 @@ hipError_t launch_mfma_cand_q8(const void* X8, uint32_t dim, uint32_t n_rows, ui
                        st, a);
     return hipGetLastError();
   }
-  hipLaunchKernelGGL((mfma_topk_kernel<768, 0, 2048 + 256, 2, false, true>), dim3(*nlists), dim3(512),
-                     0, st, a);
+  // split workgroups: two 4-wave blocks (wave parity 0 / 1) per logical
+  // workgroup; *nlists, the slabs, counts and maxima keep their logical shape
+  hipLaunchKernelGGL((mfma_topk_kernel<768, 0, 2048 + 256 + kMfVarSplit, 2, false, true>),
+                     dim3(2 * *nlists), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

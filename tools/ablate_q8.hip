@@ -2,7 +2,9 @@
 // item 2). Builds the pass in several modes and times them interleaved in
 // one process on one resident corpus, each timing a burst of back-to-back
 // launches (sustained clocks, the serving regime):
-//   prod     mfma_topk_kernel<768, 0, 2304, 2, false, true> (the product)
+//   prod     mfma_topk_kernel<768, 0, 2304, 2, false, true>: the 8-wave
+//            workgroup, the product until the split workgroups replaced it
+//            (prod-sw below is what the library launches)
 //   noapp    the same, never appending (timing only: wrong answers)
 //   noepi    MODE 1: no epilogue at all (MFMA + LDS reads + stream + barriers)
 //   stream   the bf16 kernel at D = 384 (768-B rows: the int8 pass's byte
@@ -15,6 +17,16 @@
 //            query-half mapping replaced (VAR 4096: 32 queries x 32 rows a
 //            wave, two ds_read_b128 a step; the same bytes out). The library
 //            launches the query-half kernel only.
+//   *-sw     prod, noapp, noepi, stream8 and mfma8 as split workgroups (VAR
+//            268435456: two 4-wave blocks per logical workgroup, 2 x nwg
+//            blocks of 256 threads, a 72 KiB ring each; the same bytes out),
+//            next to the 8-wave arms in the same rotation. stream8 is the
+//            int8 instance's own LDS-DMA stream alone (MODE 2). prod-sw is
+//            the product; the 8-wave instance stays in this tool only.
+// After the timings: one launch of each of the 8-wave and split clock arms
+// (VAR 8192); the split one also reports where the hardware placed the
+// blocks (q8-sw_resident_*: all blocks started before any ended, blocks per
+// CU, and whether every SIMD of a CU holds one wave of each of its blocks).
 // noepi and stream use the product's branch-free stream, as every mode of the
 // kernel that streams. The experiment arms once timed here (pair, epipipe,
 // spread, prea, split, pd2/pd3, stag, pair+epi, the sample pass's early ring
@@ -54,9 +66,10 @@ template <int D, int MODE, int VAR, bool I8>
 static float run(const Ctx& c) {
   const MfArgs& a = I8 ? c.q8 : c.bf;
   hipEventRecord(c.a, 0);
+  constexpr bool kSw = (VAR & kMfVarSplit) != 0;  // split workgroups: twice the blocks of 4 waves
   for (int i = 0; i < c.burst; ++i)
-    hipLaunchKernelGGL((mfma_topk_kernel<D, MODE, VAR, 2, false, I8>), dim3(c.nwg), dim3(512), 0, 0,
-                       a);
+    hipLaunchKernelGGL((mfma_topk_kernel<D, MODE, VAR, 2, false, I8>), dim3(kSw ? 2 * c.nwg : c.nwg),
+                       dim3(kSw ? 256 : 512), 0, 0, a);
   hipEventRecord(c.b, 0);
   hipEventSynchronize(c.b);
   float ms = 0;
@@ -134,6 +147,12 @@ int main(int argc, char** argv) {
       {"noapp-rm", run<768, 0, 2304 + 4096 + 16777216, true>, {}},
       {"noepi-rm", run<768, 1, 2304 + 4096, true>, {}},
       {"mfma8-rm", run<768, 4, 2304 + 4096, true>, {}},
+      {"stream8", run<768, 2, 2304, true>, {}},
+      {"prod-sw", run<768, 0, 2304 + kMfVarSplit, true>, {}},
+      {"noapp-sw", run<768, 0, 2304 + kMfVarSplit + 16777216, true>, {}},
+      {"noepi-sw", run<768, 1, 2304 + kMfVarSplit, true>, {}},
+      {"stream8-sw", run<768, 2, 2304 + kMfVarSplit, true>, {}},
+      {"mfma8-sw", run<768, 4, 2304 + kMfVarSplit, true>, {}},
   };
   // an arm's name as the 4th argument: that arm alone (PMC passes), R x B launches
   if (argc > 4) {
@@ -232,6 +251,66 @@ int main(int argc, char** argv) {
       printf(", \"q8%s_clk_prologue_us_med\": %.2f, \"q8%s_clk_prologue_us_max\": %.2f", rm ? "-rm" : "",
              v[v.size() / 2], rm ? "-rm" : "", v.back());
     }
+  }
+  // the split instance's clocks and residency: 8 words per physical block
+  // (4 clocks, then the hardware id of each of its 4 waves)
+  {
+    const uint32_t nb = 2 * c.nwg;
+    uint64_t* clkb;
+    CK(hipMalloc(&clkb, (size_t)nb * 8 * 8));
+    MfArgs qa = c.q8;
+    qa.lists = clkb;
+    for (int i = 0; i < 3; ++i)
+      hipLaunchKernelGGL((mfma_topk_kernel<768, 0, 2304 + kMfVarSplit + 8192, 2, false, true>), dim3(nb),
+                         dim3(256), 0, 0, qa);
+    CK(hipDeviceSynchronize());
+    std::vector<uint64_t> h((size_t)nb * 8);
+    CK(hipMemcpy(h.data(), clkb, h.size() * 8, hipMemcpyDeviceToHost));
+    uint64_t last_start = 0, first_end = ~0ull;
+    std::vector<double> v;
+    for (uint32_t b = 0; b < nb; ++b) {
+      last_start = std::max(last_start, h[8 * b]);
+      first_end = std::min(first_end, h[8 * b + 3]);
+      v.push_back((h[8 * b + 1] - h[8 * b]) * 0.01);
+    }
+    std::sort(v.begin(), v.end());
+    // a CU: (XCC, SE, SH, CU) of the id word; a block's four waves must sit on
+    // one CU, on four different SIMDs
+    std::vector<std::pair<uint32_t, uint32_t>> cu_of;  // (cu key, simd mask) per block
+    bool one_cu = true;
+    for (uint32_t b = 0; b < nb; ++b) {
+      uint32_t key0 = 0, mask = 0;
+      for (int wv = 0; wv < 4; ++wv) {
+        const uint64_t id = h[8 * b + 4 + wv];
+        const uint32_t hw = (uint32_t)id, xcc = (uint32_t)(id >> 32) & 0xFu;
+        const uint32_t key = (xcc << 16) | (hw & 0xFF00u);
+        if (wv == 0) key0 = key;
+        one_cu &= key == key0;
+        mask |= 1u << ((hw >> 4) & 3u);
+      }
+      cu_of.push_back({key0, mask});
+    }
+    std::sort(cu_of.begin(), cu_of.end());
+    uint32_t cus = 0, min_b = ~0u, max_b = 0, simd_ok = 1;
+    for (size_t i = 0; i < cu_of.size();) {
+      size_t j = i;
+      while (j < cu_of.size() && cu_of[j].first == cu_of[i].first) {
+        simd_ok &= cu_of[j].second == 0xFu;  // one wave of this block on every SIMD
+        ++j;
+      }
+      ++cus;
+      min_b = std::min(min_b, (uint32_t)(j - i));
+      max_b = std::max(max_b, (uint32_t)(j - i));
+      i = j;
+    }
+    printf(", \"q8-sw_clk_prologue_us_med\": %.2f, \"q8-sw_clk_prologue_us_max\": %.2f", v[v.size() / 2],
+           v.back());
+    printf(", \"q8-sw_resident_blocks\": %u, \"q8-sw_resident_all_started_before_any_end\": %d, "
+           "\"q8-sw_resident_start_to_first_end_us\": %.2f, \"q8-sw_resident_cus\": %u, "
+           "\"q8-sw_resident_blocks_per_cu_min\": %u, \"q8-sw_resident_blocks_per_cu_max\": %u, "
+           "\"q8-sw_resident_block_on_one_cu\": %d, \"q8-sw_resident_one_wave_per_simd\": %u",
+           nb, (int)(last_start < first_end), ((double)first_end - (double)last_start) * 0.01, cus, min_b,
+           max_b, (int)one_cu, simd_ok);
   }
   printf("}\n");
   return 0;

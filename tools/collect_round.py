@@ -22,7 +22,9 @@ def main_pass(bench):
     """The kernel name of the bench's dominant pass: the int8 prefilter pass
     when the line says so (r04), else the bf16 pass."""
     i8 = "i8" in str(bench.get("dtype", ""))
-    return f"mfma_topk_kernel<768, 0, 2304, 2, false, {'true' if i8 else 'false'}>"
+    # (the int8 pass is the split-workgroup instance: VAR 2304 + 268435456)
+    return (f"mfma_topk_kernel<768, 0, {268437760 if i8 else 2304}, 2, false, "
+            f"{'true' if i8 else 'false'}>")
 
 
 def pmc_mfma(tag, bid, kname):

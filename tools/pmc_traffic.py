@@ -17,7 +17,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # entries are that pass (the bf16 pass's launch behind it stands down at once
 # and must not enter the average), the plain ones the bf16 pass
 SCAN = {"c3": "mfma_topk_kernel<768, 0, 2304, 2, false, false>",
-        "c3_i8": "mfma_topk_kernel<768, 0, 2304, 2, false, true>",
+        # (2304 + 268435456: the split-workgroup instance the library launches)
+        "c3_i8": "mfma_topk_kernel<768, 0, 268437760, 2, false, true>",
         "c5b256_i8": "mfma_topk_kernel<1024, 0, 256, 1, false, true>",
         "c3b1": "gemv_topk_kernel<768, true, 1",
         # (r05) one query on the int8 copy: its scan kernel
