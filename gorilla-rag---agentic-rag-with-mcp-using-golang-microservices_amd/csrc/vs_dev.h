@@ -276,7 +276,6 @@ struct DevEngine {
   DevBuf q8_q, q8_par, q8_tiles;    // int8 prefilter: int8 queries, {sqS, a, c, sigma} + gate,
                                     // tiles an upsert touched
   DevBuf cand, cand_cnt;            // MFMA main pass candidates (vs_kernels.h)
-  DevBuf merge_tmp;                 // first stage of a two-stage GEMV merge
   DevBuf scand;                     // MFMA sample pass tile maxima
   DevBuf scratch8;                  // u64 result of the snapshot checksum
   DevBuf allow;                     // filter pre-mask of the current vs_search_filtered

@@ -189,14 +189,28 @@ int grow(DevEngine* eng, Collection& c, uint64_t need) {
   return VS_OK;
 }
 
+// ---- environment knobs -------------------------------------------------------
+// Each knob below is a function that reads its variable once, at first use,
+// through one of these. A flag that is on by default is cleared by a value
+// starting with '0', one that is off by default is set by one starting with '1'.
+bool env_flag(const char* name, bool dflt) {
+  const char* e = std::getenv(name);
+  return dflt ? !(e && e[0] == '0') : (e && e[0] == '1');
+}
+long env_long(const char* name, long dflt) {
+  const char* e = std::getenv(name);
+  return e ? std::atol(e) : dflt;
+}
+double env_double(const char* name) {  // unset = 0
+  const char* e = std::getenv(name);
+  return e ? std::atof(e) : 0.0;
+}
+
 // ---- int8 prefilter copy (vs_kernels.h "int8 prefilter") ------
 // On by default; VS_Q8=0 (read once) makes no copy, and batched searches then
 // read the bf16 rows only.
 bool q8_enabled() {
-  static const bool v = [] {
-    const char* e = std::getenv("VS_Q8");
-    return !(e && e[0] == '0');
-  }();
+  static const bool v = env_flag("VS_Q8", true);
   return v;
 }
 
@@ -233,10 +247,7 @@ int q8_after_write_impl(DevEngine* eng, Collection& c, uint64_t r0, uint64_t r1,
 // the bf16 / f32 pass until the next full rebuild).
 // VS_Q8_FAIL_AFTER_WRITE=1 (tests only, read once) injects such a failure.
 bool q8_fail_injected() {
-  static const bool v = [] {
-    const char* e = std::getenv("VS_Q8_FAIL_AFTER_WRITE");
-    return e && e[0] == '1';
-  }();
+  static const bool v = env_flag("VS_Q8_FAIL_AFTER_WRITE", false);
   return v;
 }
 
@@ -394,26 +405,6 @@ int device_checksum(DevEngine* eng, const Collection& c, uint64_t* out) {
 // -> keys d_keys[i * k], one scan + merge per query. For bf16 collections qp
 // already holds bf16-rounded values (search_core's query prep). With `gather`
 // (n_gather device row indices) only those rows are scanned.
-// Workgroups of the first stage of a two-stage merge of L lists of k keys
-// (1 = one stage). The one-workgroup merge's fast paths cover up to 8192
-// keys at k <= 32; past that (large k over many lists) a first stage of G
-// workgroups, each over L / G lists, runs the merge in parallel. G divides
-// L and leaves >= 8 lists per group.
-uint32_t merge_groups(uint32_t L, uint32_t k) {
-  // r03: off unless VS_MERGE_TWO_STAGE=1 (read once). With the sample-bound
-  // merge one workgroup is as fast or faster at every size measured (bf16,
-  // one query: 2k rows k = 100 89.7 -> 47.6 us, 20k 71.3 -> 63.5, 12.5M
-  // 2962 -> 2953; profiles/r03_merge_two_stage_ab.jsonl)
-  static const bool two = [] {
-    const char* e = std::getenv("VS_MERGE_TWO_STAGE");
-    return e && e[0] == '1';
-  }();
-  if (!two || k <= 32 || (uint64_t)L * k <= 8192) return 1;
-  for (uint32_t g = 64; g >= 4; --g)
-    if (L % g == 0 && L / g >= 8) return g;
-  return 1;
-}
-
 int search_gemv(DevEngine* eng, Collection& c, float* qp, uint32_t q0, uint32_t n, uint32_t k,
                 uint64_t* d_keys, const uint64_t* allow = nullptr,
                 const uint32_t* gather = nullptr, uint32_t n_gather = 0,
@@ -424,11 +415,9 @@ int search_gemv(DevEngine* eng, Collection& c, float* qp, uint32_t q0, uint32_t 
   const uint32_t row_base = (uint32_t)c.row_base;
   const uint32_t maxl = vsk::gemv_max_lists(dim, bf16, n_rows, k);
   const size_t lbytes = (size_t)maxl * k * 8;
-  const size_t mbytes = (size_t)64 * k * 8;  // two-stage merge: <= 64 groups
-  if (eng->lists.bytes < lbytes || eng->merge_tmp.bytes < mbytes) {
+  if (eng->lists.bytes < lbytes) {
     VS_HIP(hipStreamSynchronize(eng->stream), "sync");
     VS_HIP(eng->lists.ensure(lbytes), "alloc list scratch");
-    VS_HIP(eng->merge_tmp.ensure(mbytes), "alloc merge scratch");
   }
   for (uint32_t i = q0; i < q0 + n; ++i) {
     uint32_t L = 0;
@@ -438,19 +427,7 @@ int search_gemv(DevEngine* eng, Collection& c, float* qp, uint32_t q0, uint32_t 
            "gemv scan");
     VS_HIP(ev_end(eng, eng->scan_ev), "event");
     VS_HIP(ev_begin(eng, eng->merge_ev), "event");
-    const uint32_t G = merge_groups(L, k);
-    if (G > 1) {
-      // two stages: G workgroups each take the top k of L / G lists, then
-      // one merges the G lists (exact: the global top k is among the groups'
-      // top k). One workgroup over 768 x 100 keys took 195 us (12.5M rows,
-      // k = 100: 6% of the step).
-      VS_HIP(vsk::launch_merge(eng->lists.as<uint64_t>(), L / G, k, (uint64_t)(L / G) * k, G, k,
-                               k, eng->merge_tmp.as<uint64_t>(), eng->stream),
-             "merge (groups)");
-      VS_HIP(vsk::launch_merge(eng->merge_tmp.as<uint64_t>(), G, k, 0, 1, k, k,
-                               d_keys + (size_t)(i - q0) * k, eng->stream),
-             "merge");
-    } else if (direct && n == 1) {  // the keys and the completion word to the host
+    if (direct && n == 1) {  // the keys and the completion word to the host
       VS_HIP(vsk::launch_merge(eng->lists.as<uint64_t>(), L, k, 0, 1, k, k, direct->keys,
                                eng->stream, direct->flag, direct->seq),
              "merge");
@@ -481,19 +458,13 @@ int search_gemv(DevEngine* eng, Collection& c, float* qp, uint32_t q0, uint32_t 
 // The large-k selection in two launches (on unless VS_RSEL_FUSED=0; read
 // once): rsel_f1/f2 instead of the 12-launch digit chain.
 bool rsel_fused() {
-  static const bool v = [] {
-    const char* e = std::getenv("VS_RSEL_FUSED");
-    return !(e && e[0] == '0');
-  }();
+  static const bool v = env_flag("VS_RSEL_FUSED", true);
   return v;
 }
 
 uint32_t large_k_from() {
-  static const uint32_t v = [] {
-    const char* e = std::getenv("VS_LARGE_K_FROM");
-    const long x = e ? std::atol(e) : (long)vsk::kMfmaMaxK + 1;
-    return (uint32_t)std::min<long>(std::max<long>(x, 1), (long)vsk::kMaxK + 1);
-  }();
+  static const uint32_t v = (uint32_t)std::min<long>(
+      std::max<long>(env_long("VS_LARGE_K_FROM", (long)vsk::kMfmaMaxK + 1), 1), (long)vsk::kMaxK + 1);
   return v;
 }
 
@@ -576,10 +547,7 @@ int merge_any(DevEngine* eng, const uint64_t* lists, uint32_t L, uint64_t lstrid
 // select reads only the quarters that can hold a top-k key (r04; default on,
 // VS_SELECT_QMAX=0 gives back the select that re-reads every slab; read once).
 bool select_qmax() {
-  static const bool v = [] {
-    const char* e = std::getenv("VS_SELECT_QMAX");
-    return !(e && e[0] == '0');
-  }();
+  static const bool v = env_flag("VS_SELECT_QMAX", true);
   return v;
 }
 
@@ -589,60 +557,35 @@ bool select_qmax() {
 // collections run on a speculative bound once the context has learned the
 // collection's ratio for a k' >= k (r05); 0 = the sample path always
 bool q8_spec_enabled() {
-  static const bool v = [] {
-    const char* e = std::getenv("VS_Q8_SPEC");
-    return !(e && e[0] == '0');
-  }();
+  static const bool v = env_flag("VS_Q8_SPEC", true);
   return v;
 }
 // VS_Q8_SPEC_FORCE_FAIL=1 (tests only, read once): speculative batches run on
 // a ratio of 12.08 (0x41 bytes), far above any unit-vector score, so every
 // one fails its check and the gated sample path must answer it
 bool q8_spec_force_fail() {
-  static const bool v = [] {
-    const char* e = std::getenv("VS_Q8_SPEC_FORCE_FAIL");
-    return e && e[0] == '1';
-  }();
+  static const bool v = env_flag("VS_Q8_SPEC_FORCE_FAIL", false);
   return v;
 }
 
 double q8_sample_scale() {
-  static const double v = [] {
-    const char* e = std::getenv("VS_Q8_SAMPLE");
-    return e ? std::atof(e) : 0.0;
-  }();
+  static const double v = env_double("VS_Q8_SAMPLE");
   return v;
 }
 
-// VS_Q8_PREP_APART=1: the int8 queries in their own launch (the r04 form
-// before the fused bound + query launch; ablation only, read once)
 // VS_Q8_SEL_VERIFY=1 (ablation): the batch's check / record by the int8
 // select's last workgroup instead of a launch of its own after the select.
 // One launch fewer, and no faster: 0.2768 / 0.2776 against 0.2763 / 0.2759 ms
 // at the N = 8 share, C3 level (profiles/r06_sel_verify_ab.json) -- the last
 // workgroup's hand-off costs what the launch did.
 bool q8_sel_verify() {
-  static const bool v = [] {
-    const char* e = std::getenv("VS_Q8_SEL_VERIFY");
-    return e && e[0] == '1';
-  }();
-  return v;
-}
-
-bool q8_prep_apart() {
-  static const bool v = [] {
-    const char* e = std::getenv("VS_Q8_PREP_APART");
-    return e && e[0] == '1';
-  }();
+  static const bool v = env_flag("VS_Q8_SEL_VERIFY", false);
   return v;
 }
 
 // VS_SAMPLE_SCALE=<factor>: the same for the bf16 / f32 pass (ablation only)
 double plain_sample_scale() {
-  static const double v = [] {
-    const char* e = std::getenv("VS_SAMPLE_SCALE");
-    return e ? std::atof(e) : 0.0;
-  }();
+  static const double v = env_double("VS_SAMPLE_SCALE");
   return v;
 }
 
@@ -840,7 +783,7 @@ int search_mfma(DevEngine* eng, Collection& c, float* qp, uint32_t nq, uint32_t 
         VS_HIP(vsk::launch_mfma_sample(X, f32, dim, n_rows, row_base, qptr(q0 + s0), ns, k, st,
                                        tmax, maxl, &L, eng->stream, allow, run_if),
                "mfma sample scan");
-        if (s0 == 0 && (!q8_prep_apart() || run_if)) {
+        if (s0 == 0) {
           VS_HIP(vsk::launch_sample_bound_q8(tmax, L * st, ns, k, bound, qptr(q0), f32, nv, dim,
                                              c.q8_glob, q8q, q8par, run_if ? nullptr : gate,
                                              eng->stream, run_if),
@@ -926,17 +869,14 @@ int search_mfma(DevEngine* eng, Collection& c, float* qp, uint32_t nq, uint32_t 
   return VS_OK;
 }
 
-int gemv_one();
+bool gemv_one();
 uint32_t large_k_from();
 
 // One query on the int8 copy (r05; on unless VS_Q8_GEMV=0, read
 // once): a collection with an int8 copy streams it instead of its rows, and
 // the bracketed survivors are rescored on the GEMV's own arithmetic.
 bool q8_gemv_enabled() {
-  static const bool v = [] {
-    const char* e = std::getenv("VS_Q8_GEMV");
-    return !(e && e[0] == '0');
-  }();
+  static const bool v = env_flag("VS_Q8_GEMV", true);
   return v;
 }
 bool q8_gemv_path(const Collection& c, uint32_t nq, uint32_t k) {
@@ -954,7 +894,7 @@ bool small_path(const Collection& c, uint32_t nq, uint32_t k, bool filtered) {
 // small path does not): its query may then travel in the kernel arguments
 bool gemv_one_path(const Collection& c, uint32_t nq, uint32_t k) {
   return nq == 1 && c.rows > 0 && c.row_base + c.rows < 0xFFFFFFFFull &&
-         !small_path(c, nq, k, false) && k < large_k_from() && gemv_one() == 2 &&
+         !small_path(c, nq, k, false) && k < large_k_from() && gemv_one() &&
          vsk::gemv_one_ok(c.dim, k) && !q8_gemv_path(c, nq, k);
 }
 
@@ -979,8 +919,9 @@ int search_core(DevEngine* eng, Collection& c, const float* d_q, uint32_t nq, ui
   // one query over a small collection (config C1): prep, scan and merge in
   // one launch (the same keys as the three launches below, bit for bit)
   constexpr size_t kPartBytes = (size_t)vsk::kGemvSmallMaxParts * vsk::kGemvSmallMaxK * 8;
-  // the small path's parts + counter, and the one-launch GEMV's counter (the
-  // word after it): zeroed once, left zero by the kernels
+  // the small path's parts + counter, and the int8 single-query scan's two
+  // counters (from the second word after it): zeroed once, left zero by the
+  // kernels
   auto ensure_counters = [&]() -> int {
     if (eng->small_part.bytes < kPartBytes + 64) {
       VS_HIP(hipStreamSynchronize(eng->stream), "sync");
@@ -1055,37 +996,28 @@ int search_core(DevEngine* eng, Collection& c, const float* d_q, uint32_t nq, ui
     if (direct) direct->used = true;
     return VS_OK;
   }
-  // one query on the GEMV list path: query prep, scan and merge in one launch
-  // (the last workgroup merges), the answer straight to the host with `direct`
-  if (nq == 1 && !use_mfma && !gather && k < large_k_from() && gemv_one() != 0 &&
+  // one query on the GEMV list path: query prep and scan in one launch, then
+  // the merge, the answer straight to the host with `direct`
+  if (nq == 1 && !use_mfma && !gather && k < large_k_from() && gemv_one() &&
       vsk::gemv_one_ok(dim, k)) {
-    const int rc0 = ensure_counters();
-    if (rc0 != VS_OK) return rc0;
     const uint32_t maxl = vsk::gemv_max_lists(dim, bf16, (uint32_t)c.rows, k);
     if (eng->lists.bytes < (size_t)maxl * k * 8) {
       VS_HIP(hipStreamSynchronize(eng->stream), "sync");
       VS_HIP(eng->lists.ensure((size_t)maxl * k * 8), "alloc list scratch");
     }
-    const bool fused_merge = gemv_one() == 1;
     uint32_t L = 0;
     VS_HIP(ev_begin(eng, eng->scan_ev), "event");
-    VS_HIP(vsk::launch_gemv_one(
-               c.data, bf16, dim, (uint32_t)c.rows, (uint32_t)c.row_base, d_q, cosine, allow, k,
-               eng->lists.as<uint64_t>(), maxl,
-               fused_merge ? (uint32_t*)((char*)eng->small_part.p + kPartBytes + 4) : nullptr,
-               direct ? direct->keys : d_keys, eng->stream,
-               fused_merge && direct ? direct->flag : nullptr, direct ? direct->seq : 0, &L,
-               !fused_merge && direct ? direct->host_q : nullptr),
+    VS_HIP(vsk::launch_gemv_one(c.data, bf16, dim, (uint32_t)c.rows, (uint32_t)c.row_base, d_q,
+                                cosine, allow, k, eng->lists.as<uint64_t>(), maxl, eng->stream,
+                                &L, direct ? direct->host_q : nullptr),
            "gemv scan (one launch)");
     VS_HIP(ev_end(eng, eng->scan_ev), "event");
-    if (!fused_merge) {  // the workgroup lists -> launch_merge (two launches)
-      VS_HIP(ev_begin(eng, eng->merge_ev), "event");
-      VS_HIP(vsk::launch_merge(eng->lists.as<uint64_t>(), L, k, 0, 1, k, k,
-                               direct ? direct->keys : d_keys, eng->stream,
-                               direct ? direct->flag : nullptr, direct ? direct->seq : 0),
-             "merge");
-      VS_HIP(ev_end(eng, eng->merge_ev), "event");
-    }
+    VS_HIP(ev_begin(eng, eng->merge_ev), "event");
+    VS_HIP(vsk::launch_merge(eng->lists.as<uint64_t>(), L, k, 0, 1, k, k,
+                             direct ? direct->keys : d_keys, eng->stream,
+                             direct ? direct->flag : nullptr, direct ? direct->seq : 0),
+           "merge");
+    VS_HIP(ev_end(eng, eng->merge_ev), "event");
     if (direct) direct->used = true;
     return VS_OK;
   }
@@ -1163,11 +1095,7 @@ const char* last_error() { return g_last_error.c_str(); }
 
 // Search contexts per device (VS_CONTEXTS, read once; default 2, at most 8).
 int contexts_per_device() {
-  static const int v = [] {
-    const char* e = std::getenv("VS_CONTEXTS");
-    const int x = e ? std::atoi(e) : 2;
-    return x < 1 ? 1 : (x > 8 ? 8 : x);
-  }();
+  static const int v = (int)std::min<long>(std::max<long>(env_long("VS_CONTEXTS", 2), 1), 8);
   return v;
 }
 
@@ -1354,11 +1282,8 @@ int collection_drop(DevEngine* eng, const char* name) {
 
 // staging chunk: VS_UPSERT_CHUNK_MB (1..64, default 16; 4 / 8 / 32 measured slower) — an ablation knob
 size_t upsert_chunk_bytes() {
-  static const size_t v = [] {
-    const char* e = std::getenv("VS_UPSERT_CHUNK_MB");
-    const long mb = e ? std::strtol(e, nullptr, 10) : 16;
-    return (size_t)std::min(64L, std::max(1L, mb)) << 20;
-  }();
+  static const size_t v =
+      (size_t)std::min<long>(std::max<long>(env_long("VS_UPSERT_CHUNK_MB", 16), 1), 64) << 20;
   return v;
 }
 
@@ -1912,10 +1837,7 @@ uint64_t popcount_rows(const uint64_t* allow, uint64_t rows) {
 // long scan does not keep a host core busy).
 // VS_SPIN_US overrides the 60 us (read once; 0 = block at once).
 int64_t spin_us() {
-  static const int64_t v = [] {
-    const char* e = std::getenv("VS_SPIN_US");
-    return e ? (int64_t)std::atoll(e) : (int64_t)60;
-  }();
+  static const int64_t v = env_long("VS_SPIN_US", 60);
   return v;
 }
 hipError_t wait_event(hipEvent_t ev) {
@@ -2000,43 +1922,25 @@ bool wait_word(const uint64_t* w, uint64_t seq) {
 // The small path's host completion word (on unless VS_DIRECT_COMPLETION=0;
 // read once): the D2H copy + event it replaces cost ~6 us of C1's round trip.
 bool direct_completion() {
-  static const bool v = [] {
-    const char* e = std::getenv("VS_DIRECT_COMPLETION");
-    return !(e && e[0] == '0');
-  }();
+  static const bool v = env_flag("VS_DIRECT_COMPLETION", true);
   return v;
 }
 
-// One-query GEMV searches with the query prep fused into the scan
-// (VS_GEMV_ONE, read once): 2 (default) = prep + scan in one launch, then
-// the merge; 1 = the merge too, by the last workgroup; 0 = prep, scan and
-// merge as three launches.
-int gemv_one() {
-  static const int v = [] {
-    const char* e = std::getenv("VS_GEMV_ONE");
-    return e ? std::atoi(e) : 2;
-  }();
+// One-query GEMV searches with the query prep fused into the scan (on unless
+// VS_GEMV_ONE=0, read once): prep + scan in one launch, then the merge; 0 =
+// prep, scan and merge as three launches.
+bool gemv_one() {
+  static const bool v = env_flag("VS_GEMV_ONE", true);
   return v;
 }
 
 // The small path's query in the kernel arguments (on unless VS_QUERY_ARGS=0;
-// read once): no H2D copy for one-query calls on small collections.
+// read once): no H2D copy for one-query calls on small collections. The
+// one-launch GEMV form takes it the same way (one query at 2k / 20k / 200k
+// rows 31.0 / 41.0 / 127.5 -> 27.9 / 37.0 / 123.8 us,
+// profiles/r03_query_args_gemv_ab.jsonl).
 bool query_args() {
-  static const bool v = [] {
-    const char* e = std::getenv("VS_QUERY_ARGS");
-    return !(e && e[0] == '0');
-  }();
-  return v;
-}
-
-// The same for the one-launch GEMV form (on unless VS_QUERY_ARGS_GEMV=0;
-// read once): one query at 2k / 20k / 200k rows 31.0 / 41.0 / 127.5 ->
-// 27.9 / 37.0 / 123.8 us (profiles/r03_query_args_gemv_ab.jsonl).
-bool query_args_gemv() {
-  static const bool v = [] {
-    const char* e = std::getenv("VS_QUERY_ARGS_GEMV");
-    return !(e && e[0] == '0');
-  }();
+  static const bool v = env_flag("VS_QUERY_ARGS", true);
   return v;
 }
 
@@ -2121,7 +2025,7 @@ int search_host(DevEngine* eng, const char* coll, const float* queries, uint32_t
   // kernel arguments (dim <= kGemvSmallArgDim: no H2D at all)
   const bool direct = nq == 1 && !abytes && !df && k <= vsk::kMaxK && direct_completion();
   const bool qarg = direct &&
-                    (small_path(*c, nq, k, false) || (query_args_gemv() && gemv_one_path(*c, nq, k))) &&
+                    (small_path(*c, nq, k, false) || gemv_one_path(*c, nq, k)) &&
                     c->dim <= vsk::kGemvSmallArgDim && query_args();
   if (!qarg) std::memcpy(hs->in, queries, qbytes);
   // busy from the first enqueue that reads the slot: a failure after it

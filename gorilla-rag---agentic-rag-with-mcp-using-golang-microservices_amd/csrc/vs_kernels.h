@@ -131,24 +131,20 @@ hipError_t launch_gemv_small(const void* X, bool bf16, uint32_t dim, uint32_t n_
                              uint32_t* counter = nullptr, uint64_t* flag = nullptr,
                              uint64_t seq = 0, const float* q_host = nullptr);
 
-// One query in one launch (r03): the raw fp32 query q_raw (device) is
-// preprocessed by every workgroup (as launch_query_prep), the scan writes
-// per-workgroup lists to `lists` (gemv_max_lists(dim, bf16, n_rows, k)
-// entries of k keys), and the last workgroup merges them into dst[0, k) --
-// the same keys as query prep + launch_gemv + launch_merge, bit for bit.
-// `counter`: one u32, zero between launches (the kernel leaves it zero), of
-// this stream only; NULL = no merge (the lists are left for launch_merge).
-// q_host (no merge, dim <= kGemvSmallArgDim): the raw query is read from host
-// memory at launch and travels in the kernel arguments (q_raw unused). With `flag` (dst and flag mapped pinned host memory)
-// `seq` is stored to *flag once dst is host-visible. gemv_one_ok: the GEMV
+// One query, prep + scan in one launch (r03): the raw fp32 query q_raw
+// (device) is preprocessed by every workgroup (as launch_query_prep) and the
+// scan writes per-workgroup lists to `lists` (gemv_max_lists(dim, bf16,
+// n_rows, k) entries of k keys; *nlists of them) for launch_merge -- the same
+// keys as query prep + launch_gemv, bit for bit. q_host (dim <=
+// kGemvSmallArgDim): the raw query is read from host memory at launch and
+// travels in the kernel arguments (q_raw unused). gemv_one_ok: the GEMV
 // table's dims up to 1024 and k <= 128 (register lists merged per workgroup).
 bool gemv_one_ok(uint32_t dim, uint32_t k);
 hipError_t launch_gemv_one(const void* X, bool bf16, uint32_t dim, uint32_t n_rows,
                            uint32_t row_base, const float* q_raw, bool cosine,
                            const uint64_t* allow, uint32_t k, uint64_t* lists, uint32_t max_lists,
-                           uint32_t* counter, uint64_t* dst, hipStream_t st,
-                           uint64_t* flag = nullptr, uint64_t seq = 0,
-                           uint32_t* nlists = nullptr, const float* q_host = nullptr);
+                           hipStream_t st, uint32_t* nlists = nullptr,
+                           const float* q_host = nullptr);
 
 // Upper bound on the lists launch_gemv writes for these sizes.
 uint32_t gemv_max_lists(uint32_t dim, bool bf16, uint32_t n_rows, uint32_t k);
@@ -415,6 +411,8 @@ void mfma_grid(uint32_t n_rows, uint32_t* nwg, uint32_t* rows_per_wg);
 
 // Merge L sorted key lists per query -> out [nq][k] (global top-k by key).
 // List l of query q starts at lists[l * lstride + q * qstride], kin entries.
+// One workgroup per query: up to 128 keys are placed by rank, more are cut by
+// a sample bound and each list is walked down to it.
 // With `flag` (nq == 1; out and flag in mapped pinned host memory) every
 // writer fences at system scope, then `seq` is stored to *flag: the host may
 // read out once it sees seq (as launch_gemv_small's completion word).

@@ -373,23 +373,11 @@ hipError_t launch_round_bf16(const float* in, uint64_t n, float* out, hipStream_
   return hipGetLastError();
 }
 
-// merge of sorted key lists (merge_query, defined with merge_keys_kernel
-// below; the one-launch GEMV's last workgroup runs it too)
-constexpr int kMergeThreads = 512;
-constexpr int kMergeCap = 4096;
-constexpr int kMergeHeld = 16;  // fast path: keys per thread held in registers
-__device__ __forceinline__ void merge_query(const uint64_t* __restrict__ lists, uint32_t L,
-                                            uint64_t lstride, uint64_t qstride, uint32_t kin,
-                                            uint32_t k, uint32_t q, uint64_t* __restrict__ out,
-                                            uint64_t* buf, uint64_t* red, uint32_t& cnt,
-                                            bool tourney);
-
 // ---------------------------------------------------------------------------
 // single-query scan (GEMV) + per-wave top-k
 // ---------------------------------------------------------------------------
 constexpr int kGemvThreads = 512;
 constexpr int kGemvWaves = kGemvThreads / 64;
-static_assert(kGemvThreads == kMergeThreads, "the one-launch GEMV merges in its last workgroup");
 
 // Wave 0's query preprocessing into LDS, as query_prep_kernel does it (the
 // same fp64 norm in the same order, so the same bits): prep bit 0 = cosine
@@ -554,53 +542,14 @@ __device__ __forceinline__ void publish_host(uint64_t* flag, uint64_t seq) {
 
 // ONE (r03, one query, KPL <= 2, no gather): `q` is the RAW query, which
 // wave 0 of every workgroup preprocesses into LDS (prep bits as
-// query_prep_kernel), `out` receives the per-workgroup lists, and the last
-// workgroup to finish (an agent-scope counter) merges them with merge_query
-// into `dst` -- then, with `flag`, publishes `seq` there for the host. One
-// launch instead of query prep + scan + merge.
-template <int KPL>
-__device__ __forceinline__ void gemv_one_finish(const uint64_t* lists, uint32_t k,
-                                                uint32_t* counter, uint64_t* dst,
-                                                uint64_t* flag, uint64_t seq) {
-  __shared__ uint64_t buf[kMergeCap];
-  __shared__ uint64_t red[kMergeThreads / 64];
-  __shared__ uint32_t cnt;
-  __shared__ int last;
-  // hand-off (MI355X_MICROARCH.md, valid producer / consumer forms): every
-  // storing wave drains its list stores, the workgroup meets, ONE lane
-  // releases at agent scope and adds to the counter; the last adder acquires
-  // once, then the whole workgroup reads with plain loads. (A __threadfence()
-  // per thread -- an L2 write-back and an L1 invalidate per wave in every
-  // workgroup -- made a 20k-row search 3x slower.)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const uint32_t prev =
-        __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    last = prev == gridDim.x - 1;
-    if (last) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-  }
-  __syncthreads();
-  if (!last) return;
-  // the sample-bound path only (a constant: the tournament's registers would
-  // raise the scan's VGPR count)
-  merge_query(lists, gridDim.x, k, 0, k, k, 0, dst, buf, red, cnt, false);
-  if (threadIdx.x == 0) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (flag) publish_host(flag, seq);
-}
-
+// query_prep_kernel); `out` receives the per-workgroup lists for
+// launch_merge. One launch instead of query prep + scan.
 template <int D, bool BF16, int KPL, bool GATHER, int VAR, bool ONE>
 __device__ __forceinline__ void gemv_topk_body(
     const void* __restrict__ Xv, uint32_t n_rows, uint32_t row_base,
     const float* __restrict__ q, const uint64_t* __restrict__ allow, uint32_t k,
     uint32_t rows_per_wave, uint64_t* __restrict__ out, const uint32_t* __restrict__ rows,
-    uint32_t* __restrict__ hist, int prep, uint32_t* counter, uint64_t* dst, uint64_t* flag,
-    uint64_t seq) {
+    uint32_t* __restrict__ hist, int prep) {
   static_assert(!ONE || (KPL >= 1 && KPL <= 2 && !GATHER), "one-launch: list scans, no gather");
   using S = GemvShape<D, BF16>;
   constexpr bool kScores = KPL == 0;
@@ -767,9 +716,6 @@ __device__ __forceinline__ void gemv_topk_body(
       if (lhist[i]) atomicAdd(&hist[i], lhist[i]);
   } else {
     gemv_emit<KPL>(L, theta, k, lane, w, out);
-    if constexpr (ONE) {
-      if (counter) gemv_one_finish<KPL>(out, k, counter, dst, flag, seq);
-    }
   }
 }
 
@@ -779,11 +725,9 @@ __global__ __launch_bounds__(kGemvThreads) void gemv_topk_kernel(
     const float* __restrict__ q, const uint64_t* __restrict__ allow, uint32_t k,
     uint32_t rows_per_wave, uint64_t* __restrict__ out,
     const uint32_t* __restrict__ rows = nullptr, uint32_t* __restrict__ hist = nullptr,
-    int prep = 0, uint32_t* counter = nullptr, uint64_t* dst = nullptr, uint64_t* flag = nullptr,
-    uint64_t seq = 0) {
+    int prep = 0) {
   gemv_topk_body<D, BF16, KPL, GATHER, VAR, ONE>(Xv, n_rows, row_base, q, allow, k,
-                                                 rows_per_wave, out, rows, hist, prep, counter,
-                                                 dst, flag, seq);
+                                                 rows_per_wave, out, rows, hist, prep);
 }
 
 // The raw query travels in the kernel's argument segment (r03): QueryArg is
@@ -800,8 +744,7 @@ __global__ __launch_bounds__(kGemvThreads) void gemv_one_arg_kernel(
   const float* q = (const float*)(const __attribute__((address_space(4))) float*)
       __builtin_amdgcn_kernarg_segment_ptr();
   gemv_topk_body<D, BF16, KPL, false, kGemvVar, true>(Xv, n_rows, row_base, q, allow, k,
-                                                       rows_per_wave, out, nullptr, nullptr, prep,
-                                                       nullptr, nullptr, nullptr, 0);
+                                                       rows_per_wave, out, nullptr, nullptr, prep);
 }
 
 // Any dimension: one row per wave step, lane-strided scalar loads.
@@ -958,14 +901,14 @@ static hipError_t gemv_dispatch_kpl(const void* X, uint32_t n_rows, uint32_t row
 template <int D, bool BF16>
 static hipError_t gemv_one_d(const void* X, uint32_t n_rows, uint32_t row_base, const float* q_raw,
                              int prep, const uint64_t* allow, uint32_t k, uint64_t* lists,
-                             uint32_t max_lists, uint32_t* counter, uint64_t* dst, uint64_t* flag,
-                             uint64_t seq, hipStream_t st, uint32_t* nlists, const float* q_host) {
+                             uint32_t max_lists, hipStream_t st, uint32_t* nlists,
+                             const float* q_host) {
   using S = GemvShape<D, BF16>;
   const GemvGrid g = gemv_grid(n_rows, S::RB);
   if (g.nwg > max_lists) return hipErrorInvalidValue;
   if (nlists) *nlists = g.nwg;
   if constexpr (D <= (int)kGemvSmallArgDim) {
-    if (q_host) {  // no merge in the kernel (counter unused): the lists, then launch_merge
+    if (q_host) {  // the raw query in the kernel's arguments
       QueryArg<D> qa;
       std::memcpy(qa.v, q_host, sizeof(qa.v));
       if (gemv_kpl(k) == 1)
@@ -980,11 +923,11 @@ static hipError_t gemv_one_d(const void* X, uint32_t n_rows, uint32_t row_base, 
   if (gemv_kpl(k) == 1)
     hipLaunchKernelGGL((gemv_topk_kernel<D, BF16, 1, false, kGemvVar, true>), dim3(g.nwg),
                        dim3(kGemvThreads), 0, st, X, n_rows, row_base, q_raw, allow, k,
-                       g.rows_per_wave, lists, nullptr, nullptr, prep, counter, dst, flag, seq);
+                       g.rows_per_wave, lists, nullptr, nullptr, prep);
   else
     hipLaunchKernelGGL((gemv_topk_kernel<D, BF16, 2, false, kGemvVar, true>), dim3(g.nwg),
                        dim3(kGemvThreads), 0, st, X, n_rows, row_base, q_raw, allow, k,
-                       g.rows_per_wave, lists, nullptr, nullptr, prep, counter, dst, flag, seq);
+                       g.rows_per_wave, lists, nullptr, nullptr, prep);
   return hipGetLastError();
 }
 
@@ -1001,19 +944,16 @@ bool gemv_one_ok(uint32_t dim, uint32_t k) {
 hipError_t launch_gemv_one(const void* X, bool bf16, uint32_t dim, uint32_t n_rows,
                            uint32_t row_base, const float* q_raw, bool cosine,
                            const uint64_t* allow, uint32_t k, uint64_t* lists, uint32_t max_lists,
-                           uint32_t* counter, uint64_t* dst, hipStream_t st, uint64_t* flag,
-                           uint64_t seq, uint32_t* nlists, const float* q_host) {
-  if (!gemv_one_ok(dim, k) || n_rows == 0 || (counter && !dst)) return hipErrorInvalidValue;
-  if (q_host && (counter || dim > kGemvSmallArgDim)) return hipErrorInvalidValue;
+                           hipStream_t st, uint32_t* nlists, const float* q_host) {
+  if (!gemv_one_ok(dim, k) || n_rows == 0) return hipErrorInvalidValue;
+  if (q_host && dim > kGemvSmallArgDim) return hipErrorInvalidValue;
   const int prep = (cosine ? 1 : 0) | (bf16 ? 2 : 0);
 #define VS_ONE_CASE(DD)                                                                      \
   case DD:                                                                                   \
     return bf16 ? gemv_one_d<DD, true>(X, n_rows, row_base, q_raw, prep, allow, k, lists,    \
-                                       max_lists, counter, dst, flag, seq, st, nlists,       \
-                                       q_host)                                               \
+                                       max_lists, st, nlists, q_host)                        \
                 : gemv_one_d<DD, false>(X, n_rows, row_base, q_raw, prep, allow, k, lists,   \
-                                        max_lists, counter, dst, flag, seq, st, nlists,      \
-                                        q_host);
+                                        max_lists, st, nlists, q_host);
   switch (dim) {
     VS_ONE_CASE(128)
     VS_ONE_CASE(256)
@@ -3324,9 +3264,9 @@ hipError_t launch_select_slabs(const float* slabs, const uint32_t* slab_tile,
 // recomputed from the int8 copy, and more survivors than the LDS buffer holds
 // stream through a running top k (r05); nothing is handed to another pass.
 
-// SV (timing ablation, VS_Q8_SEL_SV): return after stage SV. F32: fp32 rows
-// and queries, survivors rescored on the f32 pass's v_mfma_f32_16x16x4_f32
-// chain (four MFMAs per 16-B fragment, as that pass), so again its bits.
+// F32: fp32 rows and queries, survivors rescored on the f32 pass's
+// v_mfma_f32_16x16x4_f32 chain (four MFMAs per 16-B fragment, as that pass),
+// so again its bits.
 // The int8 copy's rows, the queries' int8 images and what the select's slow
 // path needs to recompute a lossy quarter (r05): its workgroup's rows
 // [wg * rows_per_wg, ...) of the static split (mfma_grid), the pre-mask.
@@ -3384,15 +3324,15 @@ __device__ __forceinline__ int q8_row_dot(const int8_t* __restrict__ xr, const i
   return d;
 }
 
-template <int D, int SV, bool F32>
+template <int D, bool F32>
 __device__ __forceinline__ void select_q8_body(
     const f32x4_t* __restrict__ slabs, const uint32_t* __restrict__ tiles,
     const uint32_t* __restrict__ cnt, const int* __restrict__ cmax, uint32_t nwg, uint32_t cap,
     uint32_t k, uint64_t* __restrict__ out, uint32_t row_base, const void* __restrict__ X,
     const void* __restrict__ qb, uint32_t dim, const f32x4_t* __restrict__ q8par,
     const float* __restrict__ q8glob, const float* __restrict__ meta,
-    const float* __restrict__ bound, const Q8Rows r8, uint32_t two_from, uint32_t opts,
-    uint32_t* __restrict__ stats, uint64_t* __restrict__ clk) {
+    const float* __restrict__ bound, const Q8Rows r8, uint32_t* __restrict__ stats,
+    uint64_t* __restrict__ clk) {
   __shared__ uint64_t buf[kMfmaSelBuf];
   __shared__ uint64_t res[kMfmaSelBuf];  // rescored keys
   __shared__ uint32_t pre[4 * kMfmaMaxLists + 1];
@@ -3484,14 +3424,12 @@ __device__ __forceinline__ void select_q8_body(
   buf[l0] = (uint64_t)y0 << 32;
   buf[l0 + 1] = (uint64_t)y1 << 32;
   const uint32_t nzq = (uint32_t)__syncthreads_count(y0 != 0) + (uint32_t)__syncthreads_count(y1 != 0);
-  // opts bit 0 (VS_Q8_SEL_P0=0, ablation): no quarter bound, the sample's alone
-  const uint32_t P0 = nzq >= k && !(opts & 1u) ? kth_floor(buf, 2 * kSelThreads, k) : 0u;
+  const uint32_t P0 = nzq >= k ? kth_floor(buf, 2 * kSelThreads, k) : 0u;
   const float tl_b = b == -INFINITY ? -INFINITY : b - sig * nmax;
   const float tl_l = P0 ? vs::ord_score(P0) : -INFINITY;
   const float Tcut = tl_b > tl_l ? tl_b : tl_l;
   if (stats && tid == 0 && tl_l > tl_b) atomicAdd(stats + 3, 1u);  // (tools) the quarter bound won
   tick(1);
-  if constexpr (SV == 1) return;
   // only quarters whose largest dot can reach Tcut hold survivors
   if (c0 && (float)x0 * sqS + mg < Tcut) c0 = 0, lossy0 = false;
   if (c1 && (float)x1 * sqS + mg < Tcut) c1 = 0, lossy1 = false;
@@ -3585,7 +3523,6 @@ __device__ __forceinline__ void select_q8_body(
   }
   __syncthreads();
   tick(2);
-  if constexpr (SV == 2) return;
   const uint32_t ns = fill;
   if (stats && tid == 0) {  // (tools/q8_check.hip) slabs read, survivors
     atomicAdd(stats, T);
@@ -3802,7 +3739,7 @@ __device__ __forceinline__ void select_q8_body(
     tick(4);
     return;
   }
-  if (ns > k + 64 && ns >= two_from) {
+  if (ns > k + 64) {
     // Two rounds (r04; r05: radix floors for every k): the survivors whose U
     // image reaches P1 (the floor of the bucket of the k-th largest U: at
     // least k of them) first; P2, the floor of the k-th best exact score
@@ -3822,7 +3759,6 @@ __device__ __forceinline__ void select_q8_body(
   } else {
     rescore_where([&](uint64_t) { return true; });
   }
-  if constexpr (SV == 3) return;
   __syncthreads();
   tick(3);
   // the final top k: the keys whose score image reaches the floor of the
@@ -3862,22 +3798,22 @@ __device__ __forceinline__ void select_q8_body(
 // -- the batch's check (a speculative batch) or record (a sample-path one) by
 // the last workgroup to finish, the work q8_verify_record_kernel does in a
 // launch of its own (vs_spec_dev.h): each workgroup hands its query's values
-// over (vq) and takes a ticket (agent-scope release / acquire, as
-// gemv_one_finish); the last runs spec_verify_core over all of them and
-// leaves the ticket zero. run_if: stand down unless *run_if.
-template <int D, int SV = 0, bool F32 = false>
+// over (vq) and takes a ticket (agent-scope release / acquire); the last runs
+// spec_verify_core over all of them and leaves the ticket zero. run_if: stand
+// down unless *run_if.
+template <int D, bool F32 = false>
 __global__ __launch_bounds__(kSelThreads) void select_q8_kernel(
     const f32x4_t* __restrict__ slabs, const uint32_t* __restrict__ tiles,
     const uint32_t* __restrict__ cnt, const int* __restrict__ cmax, uint32_t nwg, uint32_t cap,
     uint32_t k, uint64_t* __restrict__ out, uint32_t row_base, const void* __restrict__ X,
     const void* __restrict__ qb, uint32_t dim, const f32x4_t* __restrict__ q8par,
     const float* __restrict__ q8glob, const float* __restrict__ meta,
-    const float* __restrict__ bound, const Q8Rows r8, uint32_t two_from, uint32_t opts,
-    uint32_t* __restrict__ stats, uint64_t* __restrict__ clk, const uint32_t* __restrict__ run_if,
+    const float* __restrict__ bound, const Q8Rows r8, uint32_t* __restrict__ stats,
+    uint64_t* __restrict__ clk, const uint32_t* __restrict__ run_if,
     const SpecVerifyArgs va) {
   if (run_if && *run_if == 0u) return;  // (r05) the fallback behind a verified speculative batch
-  select_q8_body<D, SV, F32>(slabs, tiles, cnt, cmax, nwg, cap, k, out, row_base, X, qb, dim, q8par,
-                             q8glob, meta, bound, r8, two_from, opts, stats, clk);
+  select_q8_body<D, F32>(slabs, tiles, cnt, cmax, nwg, cap, k, out, row_base, X, qb, dim, q8par,
+                         q8glob, meta, bound, r8, stats, clk);
   if (!va.vq) return;
   __shared__ float vrq[kMfmaQueries];
   __shared__ float vpick;
@@ -3922,35 +3858,18 @@ hipError_t launch_select_q8(const float* slabs, const uint32_t* slab_tile, const
   mfma_grid(n_rows, &gwg, &rpw);
   if (gwg != nwg) return hipErrorInvalidValue;  // the pass's static split
   const Q8Rows r8{(const int8_t*)X8, (const int8_t*)Q8, allow, n_rows, rpw, row_base};
-  // VS_Q8_TWO_ROUND_FROM (read once): the survivor count from which the
-  // select rescores in two rounds (the top k by U first, then only survivors
-  // whose U reaches their k-th exact score); below it, one round
-  static const uint32_t two_from = [] {
-    const char* e = getenv("VS_Q8_TWO_ROUND_FROM");
-    return e ? (uint32_t)atoi(e) : 0u;
-  }();
-  static const int sv = [] {
-    const char* e = getenv("VS_Q8_SEL_SV");
-    return e ? atoi(e) : 0;
-  }();
-  static const uint32_t opts = [] {
-    const char* e = getenv("VS_Q8_SEL_P0");
-    return e && atoi(e) == 0 ? 1u : 0u;
-  }();
-  decltype(&select_q8_kernel<768, 0, false>) kern;
+  decltype(&select_q8_kernel<768, false>) kern;
   if (f32 && dim == 768)
-    kern = select_q8_kernel<768, 0, true>;
+    kern = select_q8_kernel<768, true>;
   else if (!f32 && dim == 1024)
-    kern = select_q8_kernel<1024, 0, false>;
+    kern = select_q8_kernel<1024, false>;
   else if (!f32 && dim == 768)
-    kern = sv == 1 ? select_q8_kernel<768, 1> : sv == 2 ? select_q8_kernel<768, 2>
-         : sv == 3 ? select_q8_kernel<768, 3> : select_q8_kernel<768, 0>;
+    kern = select_q8_kernel<768, false>;
   else
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(kern, dim3(nq), dim3(kSelThreads), 0, st, (const f32x4_t*)slabs, slab_tile,
                      cand_cnt, (const int*)cand_max, nwg, cap, k, out, row_base, X, qb, dim,
-                     (const f32x4_t*)q8par, q8glob, meta, bound, r8, two_from, opts, stats, clk,
-                     run_if, va);
+                     (const f32x4_t*)q8par, q8glob, meta, bound, r8, stats, clk, run_if, va);
   return hipGetLastError();
 }
 
@@ -3962,6 +3881,8 @@ hipError_t launch_select_q8(const float* slabs, const uint32_t* slab_tile, const
 // candidates are streamed in chunks; survivors are appended to an LDS buffer
 // that also holds the running top-k, which is re-sorted (bitonic) only when a
 // chunk added something. Correct for any input; fast when the bound is good.
+constexpr int kMergeThreads = 512;
+constexpr int kMergeCap = 4096;
 __device__ __forceinline__ void bitonic_sort_desc(uint64_t* buf, int n_pow2) {
   for (int size = 2; size <= n_pow2; size <<= 1) {
     for (int stride = size >> 1; stride > 0; stride >>= 1) {
@@ -4094,25 +4015,17 @@ __device__ __forceinline__ bool place_survivors(uint64_t* buf, uint32_t c, uint3
   return true;
 }
 
-// Top-k of query q over L lists (merge_keys_kernel; also select_slab_kernel's
-// overflow fallback). buf holds >= kMergeCap keys; red / cnt are the
-// caller's shared scratch. One workgroup of kMergeThreads threads.
+// Top-k of query q over L lists (merge_keys_kernel; also the last workgroup
+// of gemv_q8_finish_kernel): up to 128 keys are placed by rank; more are cut
+// by a sample bound and each list is walked down to it. buf holds >=
+// kMergeCap keys; red / cnt are the caller's shared scratch. One workgroup of
+// kMergeThreads threads.
 __device__ __forceinline__ void merge_query(const uint64_t* __restrict__ lists, uint32_t L,
                                             uint64_t lstride, uint64_t qstride, uint32_t kin,
                                             uint32_t k, uint32_t q, uint64_t* __restrict__ out,
-                                            uint64_t* buf, uint64_t* red, uint32_t& cnt,
-                                            bool tourney) {
+                                            uint64_t* buf, uint64_t* red, uint32_t& cnt) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 
-  // Fast path (single-query GEMV merges and shard merges at k <= 32): all
-  // L * kin keys fit kMergeHeld per thread, so they are read in ONE memory
-  // round trip, and the top k is taken by tournament: each wave extracts its
-  // k largest (wave max by xor-shuffles, k rounds; 0 = empty; every copy of
-  // an extracted key is dropped, so a key listed twice comes out once), then
-  // wave 0 extracts the k largest of the 8 waves' winners. The
-  // general path below filters against max_l list_l[k-1], which admitted
-  // hundreds of keys here (a weak bound over many short lists) and paid a
-  // block-wide bitonic sort for them.
   const uint64_t total0 = (uint64_t)L * kin;
   // Few keys (cross-shard merges: P x k; small collections): one key per
   // thread, and each key's output slot is its rank, the number of keys above
@@ -4145,73 +4058,6 @@ __device__ __forceinline__ void merge_query(const uint64_t* __restrict__ lists, 
     for (uint32_t r = nz + t; r < k; r += kMergeThreads) out[(size_t)q * k + r] = 0;
     return;
   }
-  // (r03: off unless VS_MERGE_TOURNEY=1 -- the sample-bound path below is
-  // faster; profiles/r03_merge_tourney_ab.jsonl, r03_merge_lat.jsonl)
-  if (tourney && L >= 256 && k <= 10 && total0 <= (uint64_t)kMergeThreads * kMergeHeld) {
-    uint64_t x[kMergeHeld];
-    // every load issued unconditionally (clamped index), all in flight at
-    // once; a conditional load per key compiled to one round trip each
-#pragma unroll
-    for (int u = 0; u < kMergeHeld; ++u) {
-      const uint32_t i0 = threadIdx.x + (uint32_t)u * kMergeThreads;
-      const uint32_t i = i0 < total0 ? i0 : 0u;
-      const uint32_t l = i / kin, j = i - l * kin;
-      x[u] = lists[l * lstride + q * qstride + j];
-    }
-#pragma unroll
-    for (int u = 0; u < kMergeHeld; ++u)
-      if (threadIdx.x + (uint32_t)u * kMergeThreads >= total0) x[u] = 0;
-    auto lane_max = [&]() {
-      uint64_t m = 0;
-#pragma unroll
-      for (int u = 0; u < kMergeHeld; ++u) m = x[u] > m ? x[u] : m;
-      return m;
-    };
-    auto wave_max = [&](uint64_t v) {
-#pragma unroll
-      for (int m = 32; m >= 1; m >>= 1) {
-        const uint64_t o = __shfl_xor(v, m, 64);
-        v = o > v ? o : v;
-      }
-      return v;
-    };
-    uint64_t lm = lane_max();
-    for (uint32_t r = 0; r < k; ++r) {
-      const uint64_t wm = wave_max(lm);
-      if (lane == 0) buf[w * 32 + r] = wm;
-      if (wm != 0 && lm == wm) {  // every lane holding it drops all its copies
-#pragma unroll
-        for (int u = 0; u < kMergeHeld; ++u) x[u] = x[u] == wm ? 0ull : x[u];
-        lm = lane_max();
-      }
-    }
-    __syncthreads();
-    if (w == 0) {
-      // 8 waves x k winners: lane l holds winners l, l + 64, l + 128, l + 192
-      uint64_t y[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const uint32_t e = (uint32_t)lane + 64u * (uint32_t)u, ww = e / 32, rr = e % 32;
-        y[u] = rr < k ? buf[ww * 32 + rr] : 0ull;
-      }
-      uint64_t m2 = 0;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) m2 = y[u] > m2 ? y[u] : m2;
-      for (uint32_t r = 0; r < k; ++r) {
-        const uint64_t wm = wave_max(m2);
-        if (lane == 0) out[(size_t)q * k + r] = wm;
-        if (wm != 0 && m2 == wm) {
-#pragma unroll
-          for (int u = 0; u < 4; ++u) y[u] = y[u] == wm ? 0ull : y[u];
-          m2 = 0;
-#pragma unroll
-          for (int u = 0; u < 4; ++u) m2 = y[u] > m2 ? y[u] : m2;
-        }
-      }
-    }
-    return;
-  }
-
   // Sample bound + list walk (r03). The lists are sorted descending without
   // repeats, so the k-th largest key among the first m entries of every list
   // (a subset of the keys) has at least k keys at or above it -- k DISTINCT
@@ -4396,26 +4242,13 @@ __device__ __forceinline__ void merge_query(const uint64_t* __restrict__ lists, 
 
 __global__ __launch_bounds__(kMergeThreads) void merge_keys_kernel(
     const uint64_t* __restrict__ lists, uint32_t L, uint64_t lstride, uint64_t qstride,
-    uint32_t kin, uint32_t k, uint64_t* __restrict__ out, int tourney, uint64_t* flag,
+    uint32_t kin, uint32_t k, uint64_t* __restrict__ out, uint64_t* flag,
     uint64_t seq) {
   __shared__ uint64_t buf[kMergeCap];
   __shared__ uint64_t red[kMergeThreads / 64];
   __shared__ uint32_t cnt;
-  merge_query(lists, L, lstride, qstride, kin, k, blockIdx.x, out, buf, red, cnt, tourney != 0);
+  merge_query(lists, L, lstride, qstride, kin, k, blockIdx.x, out, buf, red, cnt);
   if (flag) publish_host(flag, seq);  // merge_query returns on block-uniform paths
-}
-
-// VS_MERGE_TOURNEY=1 (read once; ablation) gives back the register
-// tournament for k <= 10 over >= 256 lists. Off by default since r03: the
-// sample-bound path with register-held list prefixes is faster at every shape
-// measured (one query, 768 lists x 10: 10.2 against 14.2 us;
-// profiles/r03_merge_lat.jsonl)
-static int merge_tourney() {
-  static const int v = [] {
-    const char* e = getenv("VS_MERGE_TOURNEY");
-    return (e && e[0] == '1') ? 1 : 0;
-  }();
-  return v;
 }
 
 hipError_t launch_merge(const uint64_t* lists, uint32_t L, uint64_t lstride,
@@ -4424,7 +4257,7 @@ hipError_t launch_merge(const uint64_t* lists, uint32_t L, uint64_t lstride,
   if (k == 0 || k > kMaxK || nq == 0 || L == 0 || kin == 0) return hipErrorInvalidValue;
   if (flag && nq != 1) return hipErrorInvalidValue;
   hipLaunchKernelGGL(merge_keys_kernel, dim3(nq), dim3(kMergeThreads), 0, st, lists, L,
-                     lstride, qstride, kin, k, out, merge_tourney(), flag, seq);
+                     lstride, qstride, kin, k, out, flag, seq);
   return hipGetLastError();
 }
 
@@ -4453,7 +4286,7 @@ hipError_t launch_merge(const uint64_t* lists, uint32_t L, uint64_t lstride,
 //     by every row of its scan workgroup. Each finishing workgroup appends
 //     the keys of its waves' top k whose score reaches P (nothing under P can
 //     be in the top k) with one agent-scope add, and the last one
-//     (agent-scope hand-off, as gemv_one_finish) sorts that short array.
+//     (agent-scope hand-off) sorts that short array.
 // Every row of the GEMV's top k has U >= s >= k-th score >= P, so it is
 // rescored and its key is the GEMV's: the answer equals the GEMV's bit for bit.
 #ifndef VS_Q8G_LISTS
@@ -4854,6 +4687,7 @@ __global__ __launch_bounds__(kGemvThreads) void gemv_q8_finish_kernel(
     }
   }
   // 5. hand-off: the last workgroup takes the top k of the array
+  static_assert(kGemvThreads == kMergeThreads, "merge_query runs in this kernel's workgroup");
   __shared__ uint64_t mbuf[kMergeCap];
   __shared__ uint64_t red[kMergeThreads / 64];
   __shared__ uint32_t mcnt;
@@ -4891,7 +4725,7 @@ __global__ __launch_bounds__(kGemvThreads) void gemv_q8_finish_kernel(
     bitonic_sort_desc_n(mbuf, p2, kGemvThreads);
     for (uint32_t j = tid; j < k; j += kGemvThreads) dst[j] = j < N ? mbuf[j] : 0ull;
   } else {  // (P = 0: fewer than k scanned rows' bounds) every key, N lists of one
-    merge_query(cand, N, 1, 0, 1, k, 0, dst, mbuf, red, mcnt, false);
+    merge_query(cand, N, 1, 0, 1, k, 0, dst, mbuf, red, mcnt);
   }
   if (tid == 0) {
     __hip_atomic_store(&ctr[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -697,9 +697,10 @@ print(json.dumps(out))
 
 
 def test_gemv_one_launch_equals_three_launches(pkg):
-    """One query on the GEMV list path runs as ONE launch (every workgroup
-    preprocesses the raw query, the last one merges the workgroup lists) and,
-    through the host API, hands its keys over by the completion word. Its
+    """One query on the GEMV list path runs query prep and scan as ONE launch
+    (every workgroup preprocesses the raw query), then the merge of the
+    workgroup lists, which, through the host API, hands the keys over by the
+    completion word. Its
     answers must be bit-identical to query prep + scan + merge (VS_GEMV_ONE=0)
     over dims 128..1024 (1536: the three launches in both runs), both dtypes and
     metrics, 300..200k rows, k 1..128
