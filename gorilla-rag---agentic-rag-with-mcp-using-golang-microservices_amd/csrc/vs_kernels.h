@@ -163,6 +163,15 @@ uint32_t gemv_max_lists(uint32_t dim, bool bf16, uint32_t n_rows, uint32_t k);
 bool gemv_q8_ok(uint32_t dim, uint32_t k);
 uint32_t gemv_q8_lists(uint32_t n_rows);
 size_t gemv_q8_scratch_bytes(uint32_t n_rows, uint32_t k);
+// Where the launcher puts its three arrays inside `scratch` (host only; the
+// launcher and the stage tests' shim read the same struct): nscan lists of kp
+// U keys, then the scan workgroups' L images (u32), then the finish's
+// compacted keys; kp = the list length (64 for k <= 64, else 128).
+struct GemvQ8Layout {
+  uint32_t nscan, kp;
+  size_t ulist_off, lbest_off, cand_off, bytes;
+};
+GemvQ8Layout gemv_q8_layout(uint32_t n_rows, uint32_t k);
 hipError_t launch_gemv_q8(int part, const void* X, bool bf16, const int8_t* X8, const float* meta,
                           const float* glob, uint32_t dim, uint32_t n_rows, uint32_t row_base,
                           const float* q_raw, bool cosine, const uint64_t* allow, uint32_t k,

@@ -4739,12 +4739,19 @@ bool gemv_q8_ok(uint32_t dim, uint32_t k) { return (dim == 768 || dim == 1024) &
 
 uint32_t gemv_q8_lists(uint32_t n_rows) { return gemv_grid(n_rows, 4).nwg; }
 
-size_t gemv_q8_scratch_bytes(uint32_t n_rows, uint32_t k) {
-  const uint64_t nscan = gemv_q8_lists(n_rows);
-  const uint64_t kp = k <= 64 ? 64 : 128;
-  const uint64_t nfin = (nscan + kQ8gLists - 1) / kQ8gLists;
-  return (size_t)(nscan * kp * 8 + (nscan * kGemvWaves * 4 + 7) / 8 * 8 + nfin * kGemvWaves * k * 8);
+GemvQ8Layout gemv_q8_layout(uint32_t n_rows, uint32_t k) {
+  GemvQ8Layout l;
+  l.nscan = gemv_q8_lists(n_rows);
+  l.kp = k <= 64 ? 64 : 128;
+  const uint64_t nfin = ((uint64_t)l.nscan + kQ8gLists - 1) / kQ8gLists;
+  l.ulist_off = 0;
+  l.lbest_off = (size_t)l.nscan * l.kp * 8;
+  l.cand_off = l.lbest_off + ((size_t)l.nscan * kGemvWaves * 4 + 7) / 8 * 8;
+  l.bytes = l.cand_off + (size_t)(nfin * kGemvWaves * k * 8);
+  return l;
 }
+
+size_t gemv_q8_scratch_bytes(uint32_t n_rows, uint32_t k) { return gemv_q8_layout(n_rows, k).bytes; }
 
 template <int D, bool BF16, int KPL>
 static void gemv_q8_launch(int part, const void* X, const int8_t* X8, const float* meta,
@@ -4772,13 +4779,13 @@ hipError_t launch_gemv_q8(int part, const void* X, bool bf16, const int8_t* X8, 
   if (!gemv_q8_ok(dim, k) || n_rows == 0 || !X || !X8 || !meta || !glob || !q_raw || !ctr ||
       !dst || scratch_bytes < gemv_q8_scratch_bytes(n_rows, k))
     return hipErrorInvalidValue;
-  const uint32_t nscan = gemv_q8_lists(n_rows);
+  const GemvQ8Layout lay = gemv_q8_layout(n_rows, k);
+  const uint32_t nscan = lay.nscan;
   if (nscan > (uint32_t)(kQ8gHeld * kGemvThreads)) return hipErrorInvalidValue;  // > 341 CUs
-  const uint32_t kp = k <= 64 ? 64 : 128;
-  uint64_t* ulist = (uint64_t*)scratch;
-  uint32_t* lbest = (uint32_t*)(ulist + (size_t)nscan * kp);
-  uint64_t* cand =
-      (uint64_t*)((char*)lbest + ((size_t)nscan * kGemvWaves * 4 + 7) / 8 * 8);
+  const uint32_t kp = lay.kp;
+  uint64_t* ulist = (uint64_t*)((char*)scratch + lay.ulist_off);
+  uint32_t* lbest = (uint32_t*)((char*)scratch + lay.lbest_off);
+  uint64_t* cand = (uint64_t*)((char*)scratch + lay.cand_off);
   const int prep = (cosine ? 1 : 0) | (bf16 ? 2 : 0);
 #define VS_Q8G(DD, BB, KK)                                                                    \
   gemv_q8_launch<DD, BB, KK>(part, X, X8, meta, glob, n_rows, row_base, q_raw, prep, allow, k,  \

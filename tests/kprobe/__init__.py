@@ -51,6 +51,17 @@ _SIGS = {
     "select_q8": (i32, [u64, u64, u64, u64, u32, u32, u32, u32, u64, u32, u64, u64, i32, u32, u64,
                         u64, u64, u64, u64, u64, u64, u32, i32, u64, u64, u64, u64, u64, u64]),
     "q8_verify_record": (i32, [u64, u32, u32, u32, u64, u64, u64, i32, u64, u64, u64, u64]),
+    "gemv_max_lists": (u32, [u32, i32, u32, u32]),
+    "gemv_one": (i32, [u64, i32, u32, u32, u32, u64, i32, u64, u32, u64, u32, pu32]),
+    "merge": (i32, [u64, u32, u64, u64, u32, u32, u32, u64]),
+    "gemv_q8_lists": (u32, [u32]),
+    "gemv_q8_scratch_bytes": (u64, [u32, u32]),
+    "gemv_q8_ulist_off": (u64, [u32, u32]),
+    "gemv_q8_lbest_off": (u64, [u32, u32]),
+    "gemv_q8_cand_off": (u64, [u32, u32]),
+    "gemv_q8_kp": (u32, [u32, u32]),
+    "gemv_q8": (i32, [i32, u64, i32, u64, u64, u64, u32, u32, u32, u64, i32, u64, u32, u64, u64, u64,
+                      u64, u64]),
 }
 
 

@@ -1,8 +1,9 @@
 // vs_kprobe.cpp — test-only C entry points over the C++ launchers of
 // csrc/vs_kernels.h (namespace vsk), so the suite can run each stage of the
 // int8 prefilter on inputs of its own (tests/kprobe/__init__.py is the ctypes
-// loader; tests/test_q8_stages_gpu.py, test_spec_verify_gpu.py and
-// test_sample_bound_gpu.py are the users).
+// loader; tests/test_q8_stages_gpu.py, test_spec_verify_gpu.py,
+// test_sample_bound_gpu.py and, for the single-query int8 scan and finish,
+// test_q8_gemv_stages_gpu.py are the users).
 //
 // Host C++ only: no kernels and no HIP runtime call. Every pointer is a raw
 // device address (uint64_t, a torch tensor's data_ptr()), every launch goes to
@@ -184,6 +185,49 @@ int kp_select_q8(uint64_t slabs, uint64_t slab_tile, uint64_t cand_cnt, uint64_t
       P<const void>(qb), f32 != 0, dim, P<const float>(q8par), P<const float>(q8glob),
       P<const float>(meta), P<const float>(bound), P<const void>(X8), P<const void>(Q8),
       P<const uint64_t>(allow), n_rows, kSt, nullptr, nullptr, nullptr, verify ? &va : nullptr);
+}
+
+// ---- single query: the plain GEMV and the int8 scan + finish ------------------
+uint32_t kp_gemv_max_lists(uint32_t dim, int bf16, uint32_t n_rows, uint32_t k) {
+  return vsk::gemv_max_lists(dim, bf16 != 0, n_rows, k);
+}
+int kp_gemv_one(uint64_t X, int bf16, uint32_t dim, uint32_t n_rows, uint32_t row_base,
+                uint64_t q_raw, int cosine, uint64_t allow, uint32_t k, uint64_t lists,
+                uint32_t max_lists, uint32_t* nlists) {
+  return (int)vsk::launch_gemv_one(P<const void>(X), bf16 != 0, dim, n_rows, row_base,
+                                   P<const float>(q_raw), cosine != 0, P<const uint64_t>(allow), k,
+                                   P<uint64_t>(lists), max_lists, kSt, nlists, nullptr);
+}
+int kp_merge(uint64_t lists, uint32_t L, uint64_t lstride, uint64_t qstride, uint32_t nq,
+             uint32_t kin, uint32_t k, uint64_t out) {
+  return (int)vsk::launch_merge(P<const uint64_t>(lists), L, lstride, qstride, nq, kin, k,
+                                P<uint64_t>(out), kSt);
+}
+uint32_t kp_gemv_q8_lists(uint32_t n_rows) { return vsk::gemv_q8_lists(n_rows); }
+uint64_t kp_gemv_q8_scratch_bytes(uint32_t n_rows, uint32_t k) {
+  return vsk::gemv_q8_scratch_bytes(n_rows, k);
+}
+// the launcher's own scratch layout (gemv_q8_layout): byte offsets, and KP
+uint64_t kp_gemv_q8_ulist_off(uint32_t n_rows, uint32_t k) {
+  return vsk::gemv_q8_layout(n_rows, k).ulist_off;
+}
+uint64_t kp_gemv_q8_lbest_off(uint32_t n_rows, uint32_t k) {
+  return vsk::gemv_q8_layout(n_rows, k).lbest_off;
+}
+uint64_t kp_gemv_q8_cand_off(uint32_t n_rows, uint32_t k) {
+  return vsk::gemv_q8_layout(n_rows, k).cand_off;
+}
+uint32_t kp_gemv_q8_kp(uint32_t n_rows, uint32_t k) { return vsk::gemv_q8_layout(n_rows, k).kp; }
+// part: 1 = scan, 2 = finish, 3 = both; no completion flag, no stage clocks
+int kp_gemv_q8(int part, uint64_t X, int bf16, uint64_t X8, uint64_t meta, uint64_t glob,
+               uint32_t dim, uint32_t n_rows, uint32_t row_base, uint64_t q_raw, int cosine,
+               uint64_t allow, uint32_t k, uint64_t scratch, uint64_t scratch_bytes, uint64_t ctr,
+               uint64_t dst, uint64_t stats) {
+  return (int)vsk::launch_gemv_q8(part, P<const void>(X), bf16 != 0, P<const int8_t>(X8),
+                                  P<const float>(meta), P<const float>(glob), dim, n_rows, row_base,
+                                  P<const float>(q_raw), cosine != 0, P<const uint64_t>(allow), k,
+                                  P<void>(scratch), (size_t)scratch_bytes, P<uint32_t>(ctr),
+                                  P<uint64_t>(dst), kSt, nullptr, 0, P<uint32_t>(stats), nullptr);
 }
 
 // ---- the speculative check / record ----------------------------------------
