@@ -533,6 +533,10 @@ __global__ __launch_bounds__(kUniqThreads) void merge_unique_kernel(
   uint64_t* o = out + (uint64_t)q * k;
   uint32_t base = 0;
   for (uint64_t t0 = 0; t0 < per && base < k; t0 += kUniqThreads) {
+    // zeros sort last: a chunk that starts with one is padding to the end. (A
+    // chunk that keeps nothing may be 256 repeats of the previous chunk's last
+    // key, with distinct keys still behind it.)
+    if (seg[t0] == 0) break;  // uniform: every thread reads the same word
     const uint64_t i = t0 + threadIdx.x;
     const uint64_t key = i < per ? seg[i] : 0;
     const bool keep = key != 0 && (i == 0 || seg[i - 1] != key);
@@ -540,7 +544,6 @@ __global__ __launch_bounds__(kUniqThreads) void merge_unique_kernel(
     const uint32_t pos = base + block_excl_scan(keep ? 1u : 0u, wsum, &total);
     if (keep && pos < k) o[pos] = key;
     base += total;
-    if (total == 0) break;  // zeros sort last: the rest is empty
   }
   for (uint32_t j = base + threadIdx.x; j < k; j += kUniqThreads) o[j] = 0;
 }

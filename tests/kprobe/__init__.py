@@ -19,10 +19,21 @@ pu32 = ctypes.POINTER(ctypes.c_uint32)
 _CONSTS64 = ["q8_glob_bytes", "q8_spec_stat_off", "q8_spec_k_off", "q8_spec_k_size",
              "q8_spec_k_count", "q8_spec_stat_size", "spec_k_ratio_off", "spec_k_backoff_off",
              "spec_k_loose_off", "spec_k_since_off", "spec_stat_tries_off", "spec_stat_fails_off",
-             "spec_stat_skipped_off", "q8_par_bytes"]
+             "spec_stat_skipped_off", "q8_par_bytes", "rsel_state_size", "rsel_state_thr_off",
+             "rsel_state_krem_off", "rsel_state_done_off", "rsel_state_count_off"]
 _CONSTS32 = ["gate_verdict", "gate_forced", "gate_go", "q8_spec_probe", "q8_spec_max_backoff",
-             "mfma_query_slots", "mfma_max_k", "mfma_max_cand_cap"]
+             "mfma_query_slots", "mfma_max_k", "mfma_max_cand_cap", "rsel_bins", "max_k"]
 _SIGS = {
+    "device_cu_count": (u32, []),
+    "gemv_scores": (i32, [u64, i32, u32, u32, u64, u64, u64, u64]),
+    "gemv": (i32, [u64, i32, u32, u32, u32, u64, u32, u64, u32, pu32, u64]),
+    "rsel": (i32, [u64, u32, u32, u32, u64, u64, u64]),
+    "rsel_fused": (i32, [u64, u32, u32, u32, u64, u64, u64, u64, u64]),
+    "sort_keys_temp_bytes": (u64, [u64]),
+    "sort_keys_desc": (i32, [u64, u64, u64, u64, u64]),
+    "merge_large_scratch": (u64, [u32, u32, u32]),
+    "merge_large": (i32, [u64, u32, u64, u64, u32, u32, u32, u64, u64, u64]),
+    "remap_keys": (i32, [u64, u64, u32, u32, u32]),
     "mfma_grid": (None, [u32, pu32, pu32]),
     "mfma_max_lists": (u32, [u32]),
     "mfma_tiles_per_wg": (u32, [u32]),

@@ -3,7 +3,12 @@
 // int8 prefilter on inputs of its own (tests/kprobe/__init__.py is the ctypes
 // loader; tests/test_q8_stages_gpu.py, test_spec_verify_gpu.py,
 // test_sample_bound_gpu.py and, for the single-query int8 scan and finish,
-// test_q8_gemv_stages_gpu.py are the users).
+// test_q8_gemv_stages_gpu.py are the users), and each piece of the large-k
+// path (test_rsel_stages_gpu.py: both selections on score images the test
+// builds; test_large_k_stages_gpu.py: the score pass, the key sort, the sort
+// merge and the key remap). The sort merge's walk used to end at the first
+// 256-key chunk that kept nothing, which a key repeated in more than 256 lists
+// produces with distinct keys still behind it; it now ends at the zero padding.
 //
 // Host C++ only: no kernels and no HIP runtime call. Every pointer is a raw
 // device address (uint64_t, a torch tensor's data_ptr()), every launch goes to
@@ -228,6 +233,58 @@ int kp_gemv_q8(int part, uint64_t X, int bf16, uint64_t X8, uint64_t meta, uint6
                                   P<const float>(q_raw), cosine != 0, P<const uint64_t>(allow), k,
                                   P<void>(scratch), (size_t)scratch_bytes, P<uint32_t>(ctr),
                                   P<uint64_t>(dst), kSt, nullptr, 0, P<uint32_t>(stats), nullptr);
+}
+
+// ---- large k: score pass, selections, sort, sort merge, remap ------------------
+uint32_t kp_rsel_bins() { return vsk::kRselBins; }
+uint32_t kp_max_k() { return vsk::kMaxK; }
+uint64_t kp_rsel_state_size() { return sizeof(vsk::RselState); }
+uint64_t kp_rsel_state_thr_off() { return offsetof(vsk::RselState, thr); }
+uint64_t kp_rsel_state_krem_off() { return offsetof(vsk::RselState, krem); }
+uint64_t kp_rsel_state_done_off() { return offsetof(vsk::RselState, done); }
+uint64_t kp_rsel_state_count_off() { return offsetof(vsk::RselState, count); }
+uint32_t kp_device_cu_count() { return (uint32_t)vsk::device_cu_count(); }
+int kp_gemv_scores(uint64_t X, int bf16, uint32_t dim, uint32_t n_rows, uint64_t q, uint64_t allow,
+                   uint64_t sc, uint64_t hist) {
+  return (int)vsk::launch_gemv_scores(P<const void>(X), bf16 != 0, dim, n_rows, P<const float>(q),
+                                      P<const uint64_t>(allow), P<uint32_t>(sc), P<uint32_t>(hist),
+                                      kSt);
+}
+// q is the preprocessed query; no row list (rows null)
+int kp_gemv(uint64_t X, int bf16, uint32_t dim, uint32_t n_rows, uint32_t row_base, uint64_t q,
+            uint32_t k, uint64_t out, uint32_t max_lists, uint32_t* nlists, uint64_t allow) {
+  return (int)vsk::launch_gemv(P<const void>(X), bf16 != 0, dim, n_rows, row_base, P<const float>(q),
+                               k, P<uint64_t>(out), max_lists, nlists, kSt,
+                               P<const uint64_t>(allow), nullptr);
+}
+int kp_rsel(uint64_t sc, uint32_t n_rows, uint32_t row_base, uint32_t keff, uint64_t hist,
+            uint64_t state, uint64_t sel) {
+  return (int)vsk::launch_rsel(P<const uint32_t>(sc), n_rows, row_base, keff, P<uint32_t>(hist),
+                               P<vsk::RselState>(state), P<uint64_t>(sel), kSt);
+}
+int kp_rsel_fused(uint64_t sc, uint32_t n_rows, uint32_t row_base, uint32_t keff, uint64_t hist,
+                  uint64_t hist1, uint64_t ctr, uint64_t sel, uint64_t cand) {
+  return (int)vsk::launch_rsel_fused(P<const uint32_t>(sc), n_rows, row_base, keff,
+                                     P<uint32_t>(hist), P<uint32_t>(hist1), P<uint32_t>(ctr),
+                                     P<uint64_t>(sel), P<uint64_t>(cand), kSt);
+}
+uint64_t kp_sort_keys_temp_bytes(uint64_t n) { return vsk::sort_keys_temp_bytes(n); }
+int kp_sort_keys_desc(uint64_t in, uint64_t out, uint64_t n, uint64_t temp, uint64_t temp_bytes) {
+  return (int)vsk::launch_sort_keys_desc(P<const uint64_t>(in), P<uint64_t>(out), n, P<void>(temp),
+                                         (size_t)temp_bytes, kSt);
+}
+uint64_t kp_merge_large_scratch(uint32_t L, uint32_t nq, uint32_t kin) {
+  return vsk::merge_large_scratch(L, nq, kin);
+}
+int kp_merge_large(uint64_t lists, uint32_t L, uint64_t lstride, uint64_t qstride, uint32_t nq,
+                   uint32_t kin, uint32_t k, uint64_t out, uint64_t scratch,
+                   uint64_t scratch_bytes) {
+  return (int)vsk::launch_merge_large(P<const uint64_t>(lists), L, lstride, qstride, nq, kin, k,
+                                      P<uint64_t>(out), P<void>(scratch), (size_t)scratch_bytes,
+                                      kSt);
+}
+int kp_remap_keys(uint64_t keys, uint64_t n, uint32_t stride, uint32_t offset, uint32_t base) {
+  return (int)vsk::launch_remap_keys(P<uint64_t>(keys), n, stride, offset, base, kSt);
 }
 
 // ---- the speculative check / record ----------------------------------------

@@ -522,8 +522,12 @@ for L, kin, k, nd in ((8, 10, 10, 6), (8, 10, 64, 30), (40, 100, 20, 15), (40, 1
         if not np.array_equal(got[q], want):
             bad.append([L, kin, k, nd, q, got[q][:8].tolist(), want[:8].tolist()])
 # replicated lists (every list the same keys): the sample's ranks count each
-# key L times, so its bound overshoots; the merge must notice and fall back
-for L, kin, k, nd in ((5000, 64, 100, 64), (600, 100, 100, 100), (40, 100, 64, 70)):
+# key L times, so its bound overshoots; the merge must notice and fall back.
+# The last two take the sort merge (k > 1024): each key fills more than one
+# 256-key chunk of the sorted segment, and its walk must go on past a chunk
+# that holds nothing new
+for L, kin, k, nd in ((5000, 64, 100, 64), (600, 100, 100, 100), (40, 100, 64, 70),
+                      (300, 8, 1100, 8), (300, 1100, 1100, 1100)):
     nq = 2
     one = np.zeros((nq, kin), np.uint64)
     for q in range(nq):

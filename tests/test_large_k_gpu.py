@@ -9,6 +9,7 @@ equal the oracle's up to exact-score near-ties, scores within 1e-5 relative.
 Covered: fp32 / bf16, cosine / dot, table and generic dims, k just past the
 list limit, k far past it, k above the row count, single queries and
 batches, exact ties at the threshold (the row-word digits of the select),
+scores spread over hundreds of the select's first-digit buckets,
 filters (dense, selective, resident, fewer allowed rows than k), a row_base,
 a sharded engine, vs_merge_keys at large k, the /search handler at 20k and
 1M rows, and the first 128 of a large-k answer equal to the k = 128 list
@@ -109,6 +110,40 @@ def test_large_k_exact_ties(pkg, orc):
                 for i in range(3):
                     eq = np.diff(s[i, :int(c[i])]) == 0
                     assert np.all(np.diff(r[i, :int(c[i])].astype(np.int64))[eq] > 0)
+
+
+@pytest.mark.parametrize("dtype", [0, 1])
+def test_large_k_wide_score_range(pkg, orc, dtype):
+    """A dot-metric collection whose rows are scaled by +-2^e, e uniform in
+    -30..30: the scores spread over hundreds of first-digit buckets of the
+    selection on both signs (unit vectors reach a handful). Pins the score
+    pass, its histogram and the selection together on the data shape that
+    tests/test_rsel_stages_gpu.py builds by hand.
+    Every row leans towards the three queries (cosine about 0.4) before it is
+    scaled: an fp32 dot rounds relative to |x||q|, the bar is relative to |s|
+    with a 1e-6 floor meant for unit vectors, so a row of length 2^30 that is
+    nearly orthogonal to the query would miss the bar by arithmetic alone."""
+    n, dim = 9000, 256
+    rng = np.random.default_rng(21 + dtype)
+    scale = np.ldexp(rng.choice([-1.0, 1.0], n), rng.integers(-30, 31, n)).astype(np.float32)
+    Q = orc.generate(15, 0, 3, dim)
+    V = (orc.generate(14, 0, n, dim) + np.float32(0.5) * Q.sum(axis=0)) * scale[:, None]
+    X = orc.preprocess(V, False, bool(dtype))
+    Qp = orc.preprocess(Q, False, bool(dtype))
+    # the spread this case exists for: the top 11 bits of the fp32 scores' order images
+    s = (X.astype(np.float64) @ Qp[0].astype(np.float64)).astype(np.float32)
+    u = s.view(np.uint32)
+    first = np.where(u >> 31, ~u, u | np.uint32(0x80000000)) >> np.uint32(21)
+    assert np.unique(first).size > 200 and (first < 1024).sum() > 1000 and (first >= 1024).sum() > 1000
+    with pkg.VectorEngine(device=0) as eng:
+        eng.create_collection("w", dim, 1, dtype)
+        eng.upsert("w", np.arange(n), V)
+        for k in (1100, 4321, 8999):
+            s, r, c = eng.search("w", Q[:1], k)
+            assert int(c[0]) == k
+            _parity(orc, X, Qp[:1], s, r, c, k)
+            s, r, c = eng.search("w", Q, k)  # a batch of 3
+            _parity(orc, X, Qp, s, r, c, k)
 
 
 @pytest.mark.parametrize("density", [0.5, 0.02, 0.0005])
