@@ -321,6 +321,14 @@ type searchBody struct {
 	Query      []float32              `json:"query"` // decimal -> float32 directly, as main.go:28
 	TopK       int                    `json:"top_k"`
 	Filter     map[string]interface{} `json:"filter"` // accepted, not applied (main.go:30)
+	MMR        *mmrBody               `json:"mmr"`    // an extension: Qdrant's query-API mmr object
+}
+
+// mmrBody is /search's optional "mmr" object (include/vsearch_service.h): both
+// fields optional, defaults 0.5 and 0 (the engine's min(4 top_k, 128)).
+type mmrBody struct {
+	Diversity       *float64 `json:"diversity"`
+	CandidatesLimit *int     `json:"candidates_limit"`
 }
 
 type hit struct {
@@ -351,6 +359,23 @@ func (s *service) search(w http.ResponseWriter, r *http.Request) {
 		writeError(w, http.StatusBadRequest, "top_k must not be negative")
 		return
 	}
+	diversity, candidates := float32(0.5), uint32(0)
+	if m := body.MMR; m != nil {
+		if m.Diversity != nil {
+			if !(*m.Diversity >= 0 && *m.Diversity <= 1) {
+				writeError(w, http.StatusBadRequest, "Invalid request body")
+				return
+			}
+			diversity = float32(*m.Diversity)
+		}
+		if m.CandidatesLimit != nil {
+			if *m.CandidatesLimit < 0 || *m.CandidatesLimit > int(vsearch.MMRMaxCandidates) {
+				writeError(w, http.StatusBadRequest, "Invalid request body")
+				return
+			}
+			candidates = uint32(*m.CandidatesLimit)
+		}
+	}
 	log.Printf("Searching in collection: %s, TopK: %d", body.Collection, body.TopK)
 	st := s.store(body.Collection)
 	if st == nil {
@@ -371,7 +396,26 @@ func (s *service) search(w http.ResponseWriter, r *http.Request) {
 		if k > rows { // Qdrant returns min(limit, points); any limit is served
 			k = rows
 		}
-		hits, err := s.batch.search(body.Collection, body.Query, uint32(k))
+		hits, err := vsearch.Hits{}, error(nil)
+		if body.MMR != nil {
+			// one engine call per request, past the batcher; results in selection order
+			if k > int(vsearch.MMRMaxCandidates) {
+				writeError(w, http.StatusBadRequest, fmt.Sprintf(
+					"top_k must not exceed %d with mmr", vsearch.MMRMaxCandidates))
+				return
+			}
+			if candidates != 0 && candidates < uint32(k) {
+				candidates = uint32(k)
+			}
+			var hs []vsearch.Hits
+			hs, err = s.eng.SearchMMR(body.Collection, body.Query, s.dim, uint32(k), candidates,
+				diversity, 0)
+			if err == nil {
+				hits = hs[0]
+			}
+		} else {
+			hits, err = s.batch.search(body.Collection, body.Query, uint32(k))
+		}
 		if err != nil {
 			writeError(w, http.StatusInternalServerError, "Search failed: "+err.Error())
 			return

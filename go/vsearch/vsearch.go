@@ -77,6 +77,15 @@ static int vsg_search_filter_id(vs_engine* h, const char* n, const float* q, uin
                                 vsg_err* e) {
 	return vsg_fin(vs_search_filter_id(h, n, q, nq, d, k, fid, s, r, c), e);
 }
+static int vsg_search_mmr(vs_engine* h, const char* n, const float* q, uint32_t nq, uint32_t d,
+                          uint32_t k, uint32_t cand, float div, uint64_t fid, float* s, uint64_t* r,
+                          uint32_t* c, vsg_err* e) {
+	return vsg_fin(vs_search_mmr(h, n, q, nq, d, k, cand, div, fid, s, r, c), e);
+}
+static int vsg_mmr_keys(vs_engine* h, const char* n, const uint64_t* ck, uint32_t nq, uint32_t nc,
+                        uint32_t k, float div, uint64_t* o, void* st, vsg_err* e) {
+	return vsg_fin(vs_mmr_keys(h, n, ck, nq, nc, k, div, o, st), e);
+}
 static int vsg_filter_create(vs_engine* h, const char* n, const uint64_t* a, uint64_t aw,
                              uint64_t* id, vsg_err* e) {
 	return vsg_fin(vs_filter_create(h, n, a, aw, id), e);
@@ -452,6 +461,58 @@ func (e *Engine) search(name string, queries []float32, dim, k uint32, allow []u
 		out[i] = Hits{Rows: rows[lo : lo+n], Scores: scores[lo : lo+n]}
 	}
 	return out, nil
+}
+
+// MMRMaxCandidates is VS_MMR_MAX_CANDIDATES: the largest candidates_limit (and k).
+const MMRMaxCandidates = uint32(C.VS_MMR_MAX_CANDIDATES)
+
+// SearchMMR is Maximal Marginal Relevance over the exact top candidatesLimit
+// rows of every query (vs_search_mmr; 0 = min(4k, 128)): Hits come in
+// SELECTION order, each with its original score. diversity is Qdrant's
+// mmr.diversity in [0, 1] (0 = plain search); filterID (0 = none) is a filter
+// made by FilterCreate. The reference has no rerank (main.go:249-254); its
+// ingest's overlapping chunks (rag/ingest-service/main.go:293-323) are the need.
+func (e *Engine) SearchMMR(name string, queries []float32, dim, k, candidatesLimit uint32,
+	diversity float32, filterID uint64) ([]Hits, error) {
+	if dim == 0 || len(queries) == 0 || len(queries)%int(dim) != 0 {
+		return nil, fmt.Errorf("vsearch: %d floats are not whole queries of dim %d: %w",
+			len(queries), dim, ErrInvalidArg)
+	}
+	if k == 0 {
+		return nil, fmt.Errorf("vsearch: k must be at least 1: %w", ErrInvalidArg)
+	}
+	nq := len(queries) / int(dim)
+	cs := C.CString(name)
+	defer C.free(unsafe.Pointer(cs))
+	rows := make([]uint64, nq*int(k))
+	scores := make([]float32, nq*int(k))
+	count := make([]uint32, nq)
+	var ce C.vsg_err
+	rc := C.vsg_search_mmr(e.h, cs, (*C.float)(unsafe.Pointer(&queries[0])), C.uint32_t(nq),
+		C.uint32_t(dim), C.uint32_t(k), C.uint32_t(candidatesLimit), C.float(diversity),
+		C.uint64_t(filterID), (*C.float)(unsafe.Pointer(&scores[0])),
+		(*C.uint64_t)(unsafe.Pointer(&rows[0])), (*C.uint32_t)(unsafe.Pointer(&count[0])), &ce)
+	if err := check(rc, &ce); err != nil {
+		return nil, err
+	}
+	out := make([]Hits, nq)
+	for i := range out {
+		lo, n := i*int(k), int(count[i])
+		out[i] = Hits{Rows: rows[lo : lo+n], Scores: scores[lo : lo+n]}
+	}
+	return out, nil
+}
+
+// MMRKeys is the selection stage alone (vs_mmr_keys): dCand holds [nq][nCand]
+// device keys as vs_search_keys writes them, dOut receives [nq][k] keys in
+// selection order, both on `stream` (a hipStream_t; nil = the null stream).
+func (e *Engine) MMRKeys(name string, dCand, dOut unsafe.Pointer, nq, nCand, k uint32,
+	diversity float32, stream unsafe.Pointer) error {
+	cs := C.CString(name)
+	defer C.free(unsafe.Pointer(cs))
+	var ce C.vsg_err
+	return check(C.vsg_mmr_keys(e.h, cs, (*C.uint64_t)(dCand), C.uint32_t(nq), C.uint32_t(nCand),
+		C.uint32_t(k), C.float(diversity), (*C.uint64_t)(dOut), stream, &ce), &ce)
 }
 
 // Snapshot writes a collection's stored rows to path (replaces Qdrant's

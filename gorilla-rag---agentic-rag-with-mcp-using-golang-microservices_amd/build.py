@@ -43,6 +43,7 @@ SOURCES = {
     "vs_select.o": (["vs_select.hip"], ["--offload-arch=" + ARCH, "-O3"]),
     "vs_q8.o": (["vs_q8.hip"], ["--offload-arch=" + ARCH, "-O3"]),
     "vs_delete.o": (["vs_delete.hip"], ["--offload-arch=" + ARCH, "-O3"]),
+    "vs_mmr.o": (["vs_mmr.hip"], ["--offload-arch=" + ARCH, "-O3"]),
     "vs_engine.o": (["vs_engine.cpp"], ["-O2", "-Wall"]),
     "vs_api.o": (["vs_api.cpp"], ["-O2", "-Wall"]),
 }

@@ -30,6 +30,11 @@ using vsjson::Json;
 extern "C" int vs_delete(vs_engine* eng, const char* coll, uint64_t n, const uint64_t* rows,
                          uint64_t* moved_from, uint64_t* moved_to, uint64_t* n_moved)
     __attribute__((weak));
+// ... and so is vs_search_mmr: without it a /search carrying "mmr" answers 501.
+extern "C" int vs_search_mmr(vs_engine* eng, const char* coll, const float* queries, uint32_t nq,
+                             uint32_t dim, uint32_t k, uint32_t candidates_limit, float diversity,
+                             uint64_t filter_id, float* out_scores, uint64_t* out_rows,
+                             uint32_t* out_count) __attribute__((weak));
 
 namespace {
 
@@ -207,6 +212,11 @@ struct SearchRequest {  // main.go:26-31
   std::vector<float> query;
   int64_t top_k = 0;
   Json filter;  // Filter map[string]interface{}: decoded; the reference never uses it
+  // "mmr": {"diversity": number, "candidates_limit": integer} (an extension:
+  // Qdrant's query-API mmr object; include/vsearch.h "MMR search")
+  bool has_mmr = false;
+  float mmr_diversity = 0.5f;
+  uint32_t mmr_candidates = 0;  // 0: the engine's default, min(4 k, 128)
 };
 
 // A JSON number literal at b[i..) (the grammar json.Decoder accepts):
@@ -391,6 +401,40 @@ std::string decode_search_generic(const char* body, size_t len, SearchRequest* r
       req->filter = *f;
     } else if (f->kind != Json::Null && first.empty()) {
       first = "filter: not an object";
+    }
+  }
+  // "mmr" (null: absent, as a nil pointer field): both fields optional, a JSON
+  // null field keeps its default; any other type, a diversity outside [0, 1]
+  // or a candidates_limit outside [0, VS_MMR_MAX_CANDIDATES] is a decode error
+  if (const Json* m = root.field("mmr")) {
+    if (m->kind == Json::Object) {
+      req->has_mmr = true;
+      if (const Json* d = m->field("diversity")) {
+        float f;
+        if (d->kind == Json::Number) {
+          if (!vsjson::parse_float32(d->str, &f) || !(f >= 0.0f && f <= 1.0f)) {
+            if (first.empty()) first = "mmr.diversity: not in [0, 1]";
+          } else {
+            req->mmr_diversity = f;
+          }
+        } else if (d->kind != Json::Null && first.empty()) {
+          first = "mmr.diversity: not a number";
+        }
+      }
+      if (const Json* c = m->field("candidates_limit")) {
+        int64_t v;
+        if (c->kind == Json::Number) {
+          if (!vsjson::parse_int64(c->str, &v) || v < 0 || v > (int64_t)VS_MMR_MAX_CANDIDATES) {
+            if (first.empty()) first = "mmr.candidates_limit: not an integer in [0, 128]";
+          } else {
+            req->mmr_candidates = (uint32_t)v;
+          }
+        } else if (c->kind != Json::Null && first.empty()) {
+          first = "mmr.candidates_limit: not a number";
+        }
+      }
+    } else if (m->kind != Json::Null && first.empty()) {
+      first = "mmr: not an object";
     }
   }
   return first;
@@ -736,6 +780,8 @@ Response handle_search(vsvc* svc, const std::string& method, const char* body, s
   // bad request instead of returning every row.
   if (req.top_k < 0) return error_json("top_k must not be negative", 400);
   const uint64_t limit = (uint64_t)req.top_k;  // Limit: uint64(req.TopK)
+  if (req.has_mmr && !vs_search_mmr)
+    return error_json("MMR search is not supported by this engine", 501);
 
   auto cs = svc->find(req.collection);
   if (!cs) return error_json("Search failed: " + not_found(req.collection), 500);
@@ -754,7 +800,29 @@ Response handle_search(vsvc* svc, const std::string& method, const char* body, s
   // reply is encoded, so rows and UUIDs cannot change underneath.
   int rc;
   std::string err;
-  if (svc->filter_match && req.filter.kind == Json::Object && !req.filter.obj.empty()) {
+  if (req.has_mmr) {
+    // MMR (an extension; include/vsearch.h "MMR search"): one engine call per
+    // request, past the batcher (its batches are plain searches). Results come
+    // back in selection order, in the same reply shape.
+    if (k > VS_MMR_MAX_CANDIDATES)
+      return error_json("top_k must not exceed " + std::to_string(VS_MMR_MAX_CANDIDATES) +
+                            " with mmr",
+                        400);
+    uint32_t cand = req.mmr_candidates;  // 0 stays the engine's default (>= k)
+    if (cand != 0 && cand < k) cand = (uint32_t)k;
+    uint64_t fid = 0;
+    if (svc->filter_match && req.filter.kind == Json::Object && !req.filter.obj.empty()) {
+      fid = filter_mask(svc->eng, req.collection, *cs, req.filter).device_id;
+      if (!fid) {  // vs_search_mmr takes a resident filter only
+        err = last_error();  // of the vs_filter_create that failed
+        if (err.empty()) err = "the filter could not be made resident";
+        return error_json("Search failed: " + grpc_error(VS_ERR_INTERNAL, err), 500);
+      }
+    }
+    rc = vs_search_mmr(svc->eng, req.collection.c_str(), req.query.data(), 1, cs->dim, (uint32_t)k,
+                       cand, req.mmr_diversity, fid, scores.data(), hit_rows.data(), &count);
+    if (rc != VS_OK) err = last_error();
+  } else if (svc->filter_match && req.filter.kind == Json::Object && !req.filter.obj.empty()) {
     // filtered searches: through the batcher with the other requests of the
     // same resident filter, or directly
     auto f = filter_mask(svc->eng, req.collection, *cs, req.filter);

@@ -521,6 +521,51 @@ int placed_search_keys(vs_engine* E, SColl& sc, const float* d_q, uint32_t nq, u
   return VS_OK;
 }
 
+// vs_mmr_keys of a placed collection on device `home` != 0, as
+// placed_search_keys: the candidate lists (dev 0, ordered on cs) are copied to
+// the home device, selected from there on its own stream, and the result
+// copied back to d_out on dev 0; cs waits for it.
+int placed_mmr_keys(vs_engine* E, SColl& sc, const uint64_t* d_cand, uint32_t nq, uint32_t n_cand,
+                    uint32_t k, float diversity, uint64_t* d_out, hipStream_t cs) {
+  CtxSet& cx = *E->sets[0];
+  DevEngine* d0 = E->dev[0];
+  DevEngine* de = home_eng(E, sc);
+  auto& sd = cx.scr[sc.home];
+  auto c = vsd::find_coll(de, sc.iname[0].c_str());
+  if (!c) return not_found(sc.name.c_str());
+  std::shared_lock<std::shared_mutex> rl(c->mu);
+  const size_t cbytes = (size_t)nq * n_cand * 8, kbytes = (size_t)nq * k * 8;
+  std::unique_lock<std::mutex> g0(d0->work_mu, std::defer_lock), gh(de->work_mu, std::defer_lock);
+  std::lock(g0, gh);
+  VS_HIP(vsd::set_dev(d0), "hipSetDevice");
+  VS_HIP(hipEventRecord(cx.scr[0].qev, cs), "candidate event");
+  VS_HIP(vsd::set_dev(de), "hipSetDevice");
+  VS_HIP(vsd::use_stream(de, de->own), "stream order");
+  if (sd.gather.bytes < cbytes || sd.keys.bytes < kbytes) {
+    VS_HIP(hipStreamSynchronize(de->stream), "sync");
+    VS_HIP(sd.gather.ensure(cbytes), "alloc candidates");
+    VS_HIP(sd.keys.ensure(kbytes), "alloc keys");
+  }
+  VS_HIP(hipStreamWaitEvent(de->stream, cx.scr[0].qev, 0), "candidate order");
+  VS_HIP(hipMemcpyPeerAsync(sd.gather.p, de->device, d_cand, d0->device, cbytes, de->stream),
+         "candidate peer copy");
+  const int rc = vsd::mmr_core(de, *c, sd.gather.as<uint64_t>(), nq, n_cand, k, diversity,
+                               sd.keys.as<uint64_t>());
+  if (rc != VS_OK) return rc;
+  VS_HIP(hipMemcpyPeerAsync(d_out, d0->device, sd.keys.p, de->device, kbytes, de->stream),
+         "keys peer copy");
+  VS_HIP(hipEventRecord(sd.kev, de->stream), "keys event");
+  VS_HIP(vsd::set_dev(d0), "hipSetDevice");
+  VS_HIP(hipStreamWaitEvent(cs, sd.kev, 0), "keys order");
+  return VS_OK;
+}
+
+int mmr_striped() {
+  return fail(VS_ERR_INVALID_ARG,
+              "MMR search is not available on a row-striped collection (its candidates' rows "
+              "live on several devices); use a vs_open engine or VS_FLAG_PLACE_COLLECTIONS");
+}
+
 // stored rows of a sharded collection, global rows [first, first + n), in
 // global order, through per-shard reads (fp32 widened, or raw stored bytes)
 template <bool RAW>
@@ -1389,6 +1434,58 @@ int vs_search_keys(vs_engine* eng, const char* coll, const float* d_queries, uin
   if (eng->dev.size() > 1) VS_HIP(hipEventRecord(cx.scr[0].qev, cs), "query event");
   return sharded_search(eng, cx, *sc, nullptr, d_queries, true, cs, nq, k, nullptr, nullptr,
                         nullptr, nullptr, d_keys);
+}
+
+int vs_search_mmr(vs_engine* eng, const char* coll, const float* queries, uint32_t nq,
+                  uint32_t dim, uint32_t k, uint32_t candidates_limit, float diversity,
+                  uint64_t filter_id, float* out_scores, uint64_t* out_rows,
+                  uint32_t* out_count) {
+  if (!eng) return fail(VS_ERR_INVALID_ARG, "engine is NULL");
+  if (!eng->sharded)
+    return vsd::search_mmr_host(eng->dev[0], coll, queries, nq, dim, k, candidates_limit,
+                                diversity, filter_id, out_scores, out_rows, out_count);
+  if (const int rc = vsd::mmr_args(k, &candidates_limit, diversity)) return rc;
+  if (nq == 0) return VS_OK;
+  if (!queries) return fail(VS_ERR_INVALID_ARG, "queries is NULL");
+  auto sc = find_scoll(eng, coll);
+  if (!sc) return not_found(coll);
+  if (sc->home < 0) return mmr_striped();
+  uint64_t dev_fid = 0;
+  if (filter_id) {  // the home device's filter, as sharded_search_host maps it
+    std::lock_guard<std::mutex> g(eng->filt_mu);
+    auto it = eng->filters.find(filter_id);
+    if (it == eng->filters.end())
+      return fail(VS_ERR_NOT_FOUND, "filter " + std::to_string(filter_id) + " not found");
+    if (it->second.coll_gen != sc->gen)
+      return fail(VS_ERR_INVALID_ARG, "filter " + std::to_string(filter_id) +
+                                          " was built for another collection state");
+    dev_fid = it->second.dev_fid[0];
+  }
+  return vsd::search_mmr_host(home_eng(eng, *sc), sc->iname[0].c_str(), queries, nq, dim, k,
+                              candidates_limit, diversity, dev_fid, out_scores, out_rows,
+                              out_count);
+}
+
+int vs_mmr_keys(vs_engine* eng, const char* coll, const uint64_t* d_cand_keys, uint32_t nq,
+                uint32_t n_cand, uint32_t k, float diversity, uint64_t* d_out_keys,
+                void* stream) {
+  if (!eng) return fail(VS_ERR_INVALID_ARG, "engine is NULL");
+  if (const int rt = vsd::one_hip_runtime()) return rt;
+  if (!eng->sharded)
+    return vsd::mmr_keys(eng->dev[0], coll, d_cand_keys, nq, n_cand, k, diversity, d_out_keys,
+                         stream);
+  if (n_cand == 0) return fail(VS_ERR_INVALID_ARG, "n_cand must be at least 1");
+  if (const int rc = vsd::mmr_args(k, &n_cand, diversity)) return rc;
+  if (nq == 0) return VS_OK;
+  if (!d_cand_keys || !d_out_keys) return fail(VS_ERR_INVALID_ARG, "NULL device pointer");
+  auto sc = find_scoll(eng, coll);
+  if (!sc) return not_found(coll);
+  if (sc->home < 0) return mmr_striped();
+  if (sc->home == 0)
+    return vsd::mmr_keys(eng->dev[0], sc->iname[0].c_str(), d_cand_keys, nq, n_cand, k, diversity,
+                         d_out_keys, stream);
+  return placed_mmr_keys(eng, *sc, d_cand_keys, nq, n_cand, k, diversity, d_out_keys,
+                         (hipStream_t)stream);
 }
 
 int vs_merge_keys(vs_engine* eng, const uint64_t* d_lists, uint32_t n_lists, uint32_t nq,

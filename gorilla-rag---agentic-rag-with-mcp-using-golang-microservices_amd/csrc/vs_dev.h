@@ -289,6 +289,7 @@ struct DevEngine {
   // completion counter (zeroed at allocation; each launch leaves it zero)
   DevBuf small_part;
   DevBuf q8g;  // one query on the int8 copy: workgroup lists, wave bounds, candidates
+  DevBuf mmr_cand;  // vs_search_mmr: the candidate search's keys, [nq][candidates_limit]
   DevBuf del;  // vs_delete: rows, bitmaps, the pair lists, the tile list, a striped delete's
                // staged rows; kept between calls up to 64 MiB, released above (delete_rows)
   // (r05) per collection (Collection::gen): what this context has answered
@@ -360,6 +361,20 @@ int filter_create(DevEngine* eng, const char* coll, const uint64_t* allow, uint6
 int filter_drop(DevEngine* eng, uint64_t filter_id);
 int search_keys(DevEngine* eng, const char* coll, const float* d_queries, uint32_t nq,
                 uint32_t dim, uint32_t k, uint64_t* d_keys, void* stream);
+// MMR search (include/vsearch.h states the rule). mmr_args checks k,
+// candidates_limit (0 = the default, resolved in place) and diversity alone, so
+// every layout reports a bad argument before it looks at the collection.
+int mmr_args(uint32_t k, uint32_t* candidates_limit, float diversity);
+int search_mmr_host(DevEngine* eng, const char* coll, const float* queries, uint32_t nq,
+                    uint32_t dim, uint32_t k, uint32_t candidates_limit, float diversity,
+                    uint64_t filter_id, float* out_scores, uint64_t* out_rows,
+                    uint32_t* out_count);
+int mmr_keys(DevEngine* eng, const char* coll, const uint64_t* d_cand_keys, uint32_t nq,
+             uint32_t n_cand, uint32_t k, float diversity, uint64_t* d_out_keys, void* stream);
+// The selection launch alone on eng->stream; work_mu and the collection's
+// reader lock held by the caller.
+int mmr_core(DevEngine* eng, Collection& c, const uint64_t* d_cand, uint32_t nq, uint32_t n_cand,
+             uint32_t k, float diversity, uint64_t* d_out);
 int merge_keys(DevEngine* eng, const uint64_t* d_lists, uint32_t n_lists, uint32_t nq,
                uint32_t k_in, uint32_t k, uint64_t* d_out_keys, void* stream);
 // launch_merge for any k on eng->stream (k or k_in > vsk::kMaxK: the sort

@@ -2179,6 +2179,165 @@ int search_keys(DevEngine* eng, const char* coll, const float* d_queries, uint32
   return search_core(eng, *c, d_queries, nq, k, d_keys);
 }
 
+// ---- MMR search (include/vsearch.h "MMR search") ---------------------------
+
+int mmr_args(uint32_t k, uint32_t* candidates_limit, float diversity) {
+  if (k == 0) return fail(VS_ERR_INVALID_ARG, "k must be at least 1");
+  if (k > VS_MMR_MAX_CANDIDATES)
+    return fail(VS_ERR_INVALID_ARG, "k " + std::to_string(k) + " exceeds VS_MMR_MAX_CANDIDATES " +
+                                        std::to_string(VS_MMR_MAX_CANDIDATES));
+  uint32_t F = *candidates_limit;
+  if (F == 0) F = std::min<uint32_t>(std::max<uint32_t>(4 * k, k), VS_MMR_MAX_CANDIDATES);
+  if (F > VS_MMR_MAX_CANDIDATES)
+    return fail(VS_ERR_INVALID_ARG, "candidates_limit " + std::to_string(F) +
+                                        " exceeds VS_MMR_MAX_CANDIDATES " +
+                                        std::to_string(VS_MMR_MAX_CANDIDATES));
+  if (k > F)
+    return fail(VS_ERR_INVALID_ARG, "k " + std::to_string(k) + " exceeds candidates_limit " +
+                                        std::to_string(F));
+  if (!(diversity >= 0.0f && diversity <= 1.0f))  // NaN fails both comparisons
+    return fail(VS_ERR_INVALID_ARG, "diversity must be in [0, 1]");
+  *candidates_limit = F;
+  return VS_OK;
+}
+
+int mmr_core(DevEngine* eng, Collection& c, const uint64_t* d_cand, uint32_t nq, uint32_t n_cand,
+             uint32_t k, float diversity, uint64_t* d_out) {
+  if (c.rows >= 0xFFFFFFFFull || c.row_base + c.rows >= 0xFFFFFFFFull)
+    return fail(VS_ERR_INVALID_ARG, "collection exceeds 2^32-1 rows");
+  if (c.row_bytes() % 8 != 0)  // the gather reads 8-byte words, as the checksum does
+    return fail(VS_ERR_INVALID_ARG, "MMR search needs rows of whole 8-byte words "
+                                    "(bf16: dim % 4 == 0, fp32: dim % 2 == 0)");
+  VS_HIP(vsk::launch_mmr(c.data, c.dtype == VS_DTYPE_BF16, c.dim, (uint32_t)c.rows,
+                         (uint32_t)c.row_base, d_cand, nq, n_cand, k, diversity, d_out,
+                         eng->stream),
+         "mmr select");
+  return VS_OK;
+}
+
+// search_host with the selection stage between the candidate search and the
+// D2H. The reader lock spans both stages: a vs_delete cannot move a candidate's
+// row between the search that named it and the gather that reads it.
+int search_mmr_host(DevEngine* eng, const char* coll, const float* queries, uint32_t nq,
+                    uint32_t dim, uint32_t k, uint32_t candidates_limit, float diversity,
+                    uint64_t filter_id, float* out_scores, uint64_t* out_rows,
+                    uint32_t* out_count) {
+  if (!eng) return fail(VS_ERR_INVALID_ARG, "engine is NULL");
+  const int arc = mmr_args(k, &candidates_limit, diversity);
+  if (arc != VS_OK) return arc;
+  if (nq == 0) return VS_OK;
+  if (!queries) return fail(VS_ERR_INVALID_ARG, "queries is NULL");
+  auto c = find_coll(eng, coll);
+  if (!c) return fail(VS_ERR_NOT_FOUND, std::string("collection ") + (coll ? coll : "") +
+                                            " not found");
+  if (dim != c->dim)
+    return fail(VS_ERR_DIM_MISMATCH, "Vector dimension error: expected dim: " +
+                                         std::to_string(c->dim) + ", got " + std::to_string(dim));
+  std::shared_lock<std::shared_mutex> rl(c->mu);
+  if (c->row_bytes() % 8 != 0)  // before anything is enqueued (mmr_core states the rule)
+    return fail(VS_ERR_INVALID_ARG, "MMR search needs rows of whole 8-byte words "
+                                    "(bf16: dim % 4 == 0, fp32: dim % 2 == 0)");
+  // the candidate search is sized for min(F, rows), the selection for
+  // min(k, that); the caller's outputs keep their stride k
+  const uint32_t ko = k;
+  const uint32_t F = (uint32_t)std::min<uint64_t>(candidates_limit, std::max<uint64_t>(c->rows, 1));
+  k = std::min(k, F);
+  std::shared_ptr<DevFilter> df;
+  if (filter_id) {
+    df = find_filter(eng, filter_id);
+    if (!df) return fail(VS_ERR_NOT_FOUND, "filter " + std::to_string(filter_id) + " not found");
+    if (df->coll_gen != c->gen || df->rows != c->rows)
+      return fail(VS_ERR_INVALID_ARG, "filter " + std::to_string(filter_id) +
+                                          " was built for another collection state");
+  }
+  std::unique_lock<std::mutex> g;
+  DevEngine* cx = pick_context(eng, &g, heavy_search(*c, nq));
+  cx->inflight.fetch_add(1, std::memory_order_relaxed);
+  struct Leave {
+    DevEngine* cx;
+    ~Leave() { cx->inflight.fetch_sub(1, std::memory_order_relaxed); }
+  } leave{cx};
+  VS_HIP(set_dev(cx), "hipSetDevice");
+  VS_HIP(use_stream(cx, cx->own), "stream order");
+  const size_t qbytes = (size_t)nq * c->dim * 4;
+  const size_t kbytes = (size_t)nq * k * 8;
+  const size_t cbytes = (size_t)nq * F * 8;
+  if (cx->q_in.bytes < qbytes || cx->keys.bytes < kbytes || cx->mmr_cand.bytes < cbytes) {
+    VS_HIP(hipStreamSynchronize(cx->stream), "sync");
+    VS_HIP(cx->q_in.ensure(qbytes), "alloc query input");
+    VS_HIP(cx->keys.ensure(kbytes), "alloc keys");
+    VS_HIP(cx->mmr_cand.ensure(cbytes), "alloc mmr candidates");
+  }
+  HostSlot* hs = nullptr;
+  for (auto& x : cx->host_slots)
+    if (!x->busy) {
+      hs = x.get();
+      break;
+    }
+  if (!hs) {
+    cx->host_slots.push_back(std::make_unique<HostSlot>());
+    hs = cx->host_slots.back().get();
+  }
+  VS_HIP(hs->ensure(qbytes, kbytes), "alloc pinned staging");
+  std::memcpy(hs->in, queries, qbytes);
+  hs->busy = true;
+  auto abandon = [&](int rc) {
+    (void)hipStreamSynchronize(cx->stream);
+    hs->busy = false;
+    return rc;
+  };
+  hipError_t e = hipMemcpyAsync(cx->q_in.p, hs->in, qbytes, hipMemcpyHostToDevice, cx->stream);
+  if (e != hipSuccess) return abandon(fail_hip(e, "query H2D"));
+  // d = 0 selects c_0, c_1, ... in order: the answer is vs_search's for k, and
+  // is taken from that very search, so it matches it bit for bit whatever path
+  // the engine picks for k and for F (two scan kernels may round a score's
+  // last bit differently: the lists pass at k <= 16, the candidate pass above)
+  const bool plain = diversity == 0.0f;
+  uint64_t* d_cand = plain ? cx->keys.as<uint64_t>() : cx->mmr_cand.as<uint64_t>();
+  int rc;
+  if (df)
+    rc = search_core(cx, *c, cx->q_in.as<float>(), nq, plain ? k : F, d_cand,
+                     df->bits.as<uint64_t>(), df->allowed,
+                     df->list.p ? df->list.as<uint32_t>() : nullptr);
+  else
+    rc = search_core(cx, *c, cx->q_in.as<float>(), nq, plain ? k : F, d_cand);
+  if (rc == VS_OK && !plain)
+    rc = mmr_core(cx, *c, cx->mmr_cand.as<uint64_t>(), nq, F, k, diversity,
+                  cx->keys.as<uint64_t>());
+  if (rc != VS_OK) return abandon(rc);
+  e = hipMemcpyAsync(hs->out, cx->keys.p, kbytes, hipMemcpyDeviceToHost, cx->stream);
+  if (e == hipSuccess) e = hipEventRecord(hs->done, cx->stream);
+  if (e != hipSuccess) return abandon(fail_hip(e, "keys D2H"));
+  g.unlock();  // wait outside work_mu, as search_host does
+  const hipError_t we = wait_event(hs->done);
+  if (we == hipSuccess)
+    decode_host((const uint64_t*)hs->out, nq, k, out_scores, out_rows, out_count, ko);
+  g.lock();
+  hs->busy = false;
+  VS_HIP(we, "search sync");
+  return VS_OK;
+}
+
+int mmr_keys(DevEngine* eng, const char* coll, const uint64_t* d_cand_keys, uint32_t nq,
+             uint32_t n_cand, uint32_t k, float diversity, uint64_t* d_out_keys, void* stream) {
+  if (!eng) return fail(VS_ERR_INVALID_ARG, "engine is NULL");
+  if (n_cand == 0) return fail(VS_ERR_INVALID_ARG, "n_cand must be at least 1");
+  const int arc = mmr_args(k, &n_cand, diversity);
+  if (arc != VS_OK) return arc;
+  if (nq == 0) return VS_OK;
+  if (!d_cand_keys || !d_out_keys) return fail(VS_ERR_INVALID_ARG, "NULL device pointer");
+  auto c = find_coll(eng, coll);
+  if (!c) return fail(VS_ERR_NOT_FOUND, std::string("collection ") + (coll ? coll : "") +
+                                            " not found");
+  std::shared_lock<std::shared_mutex> rl(c->mu);
+  std::lock_guard<std::mutex> g(eng->work_mu);
+  VS_HIP(set_dev(eng), "hipSetDevice");
+  // on the caller's stream, ordered after the engine's previous work (a store
+  // call's writes to the rows among it)
+  VS_HIP(use_stream(eng, (hipStream_t)stream), "stream order");
+  return mmr_core(eng, *c, d_cand_keys, nq, n_cand, k, diversity, d_out_keys);
+}
+
 int merge_keys(DevEngine* eng, const uint64_t* d_lists, uint32_t n_lists, uint32_t nq,
                   uint32_t k_in, uint32_t k, uint64_t* d_out_keys, void* stream) {
   if (!eng) return fail(VS_ERR_INVALID_ARG, "engine is NULL");

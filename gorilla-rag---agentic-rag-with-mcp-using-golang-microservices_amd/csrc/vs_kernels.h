@@ -474,6 +474,19 @@ hipError_t launch_move_rows(const void* src, const uint64_t* src_rows, void* dst
 hipError_t launch_mark_tiles(const uint64_t* dst_rows, uint32_t n_pairs, uint32_t n_rows,
                              uint64_t* tbits, hipStream_t st);
 
+// MMR selection (vs_mmr.hip; include/vsearch.h "MMR search"). cand is
+// [nq][n_cand] keys as vs_search_keys writes them (a 0 key, or one whose row is
+// outside [row_base, row_base + n_rows), is an empty slot: never dereferenced);
+// out is [nq][k] keys in selection order, 0-padded past min(k, valid slots).
+// 1 <= k <= n_cand <= kMmrMaxCand, 0 <= diversity <= 1, dim x element % 8 == 0.
+// One workgroup per query: the candidates' rows X (bf16, or fp32) are gathered
+// once, their Gram matrix formed on MFMA and the greedy loop run in LDS. cand
+// and out must not overlap. Nothing but the two lists and X is touched.
+constexpr uint32_t kMmrMaxCand = kMfmaMaxK;
+hipError_t launch_mmr(const void* X, bool bf16, uint32_t dim, uint32_t n_rows, uint32_t row_base,
+                      const uint64_t* cand, uint32_t nq, uint32_t n_cand, uint32_t k,
+                      float diversity, uint64_t* out, hipStream_t st);
+
 int device_cu_count();
 
 }  // namespace vsk

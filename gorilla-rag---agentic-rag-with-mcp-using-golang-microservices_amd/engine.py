@@ -53,7 +53,9 @@ EXPORTS = (
     "vs_engine_layout", "vs_comm_unique_id", "vs_comm_init", "vs_gather_merge_keys",
     "vs_copy_last_error", "vs_build_id", "vs_collection_placement", "vs_runtime_check",
     "vs_collection_prefilter_bytes", "vs_collection_spec_stats", "vs_delete",
+    "vs_search_mmr", "vs_mmr_keys",
 )
+MMR_MAX_CANDIDATES = 128
 COMM_ID_BYTES = 128
 
 
@@ -156,6 +158,8 @@ def load_library(path: str = LIB_PATH):
         "vs_filter_create": ([vp, cp, vp, u64, vp], i32),
         "vs_filter_drop": ([vp, u64], i32),
         "vs_search_filter_id": ([vp, cp, vp, u32, u32, u32, u64, vp, vp, vp], i32),
+        "vs_search_mmr": ([vp, cp, vp, u32, u32, u32, u32, ctypes.c_float, u64, vp, vp, vp], i32),
+        "vs_mmr_keys": ([vp, cp, vp, u32, u32, u32, ctypes.c_float, vp, vp], i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -419,6 +423,33 @@ class VectorEngine:
         _check(self._L.vs_search_filter_id(self._h, name.encode(), _p(q), nq, q.shape[1], k,
                                            filter_id, _p(scores), _p(rows), _p(count)))
         return scores, rows, count
+
+    def search_mmr(self, name: str, queries: np.ndarray, k: int, candidates_limit: int = 0,
+                   diversity: float = 0.5, filter_id: int = 0):
+        """vs_search_mmr: Maximal Marginal Relevance over the exact top
+        `candidates_limit` (0: min(4 k, 128)) rows of every query. Results are in
+        SELECTION order, each with its original score; `filter_id` (0: none) is
+        a filter made by filter_create."""
+        q = np.ascontiguousarray(queries, np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        nq = q.shape[0]
+        scores = np.zeros((nq, k), np.float32)
+        rows = np.zeros((nq, k), np.uint64)
+        count = np.zeros(nq, np.uint32)
+        _check(self._L.vs_search_mmr(self._h, name.encode(), _p(q), nq, q.shape[1], k,
+                                     candidates_limit, diversity, filter_id, _p(scores),
+                                     _p(rows), _p(count)))
+        return scores, rows, count
+
+    def mmr_keys(self, name: str, d_cand_keys: int, nq: int, n_cand: int, k: int,
+                 diversity: float, d_out_keys: int, stream: int = 0):
+        """vs_mmr_keys: the selection stage alone over device candidate lists
+        ([nq][n_cand] keys as search_keys writes them) -> [nq][k] keys in
+        selection order, on `stream`."""
+        _check(self._L.vs_mmr_keys(self._h, name.encode(), ctypes.c_void_p(d_cand_keys), nq,
+                                   n_cand, k, diversity, ctypes.c_void_p(d_out_keys),
+                                   ctypes.c_void_p(stream)))
 
     def search_keys(self, name: str, d_queries: int, nq: int, dim: int, k: int, d_keys: int,
                     stream: int = 0):

@@ -314,7 +314,7 @@ int vs_search_filter_id(vs_engine* eng, const char* coll, const float* queries, 
  * The stream and the pointers must come from the HIP runtime this library
  * is linked to: in a process that maps two libamdhip64 runtimes (e.g.
  * torch's bundled copy next to /opt/rocm's) this call and every other one
- * taking caller device pointers (vs_merge_keys, vs_gather_merge_keys,
+ * taking caller device pointers (vs_mmr_keys, vs_merge_keys, vs_gather_merge_keys,
  * vs_decode_keys, vs_generate_vectors) fail with VS_ERR_DEVICE rather than
  * run unordered with the caller's work. vs_runtime_check() runs that test
  * alone (no device needed): VS_OK, or VS_ERR_DEVICE naming both runtimes. */
@@ -322,6 +322,67 @@ int vs_runtime_check(void);
 int vs_search_keys(vs_engine* eng, const char* coll, const float* d_queries,
                    uint32_t nq, uint32_t dim, uint32_t k, uint64_t* d_keys,
                    void* stream);
+
+/* ---- MMR search (diversity rerank on the device) ----------------------------
+ *
+ * Maximal Marginal Relevance over the exact top candidates (Qdrant's query
+ * API: mmr {diversity, candidates_limit}). The reference's ingest cuts
+ * documents into overlapping chunks (rag/ingest-service/main.go:293-323), so
+ * the k nearest rows are often near-duplicates; this returns k rows that are
+ * relevant and mutually different, without the rows leaving the device.
+ *
+ * For one query let c_0 .. c_{F-1} be the exact top-F of the collection in
+ * search order (score desc, row asc), F = candidates_limit, and s_i their
+ * scores: exactly the keys vs_search returns with k = F (under the filter,
+ * when filter_id != 0). Let sim(i, j) be the dot product of the STORED rows
+ * of c_i and c_j, accumulated in fp32 (the cosine for COSINE collections,
+ * whose rows are stored normalised; the inner product for DOT), and d =
+ * `diversity` as fp32.
+ *   step 0 selects c_0;
+ *   step t >= 1, S the set selected so far: every unselected i gets
+ *     v_i = (1 - d) * s_i - d * max_{j in S} sim(i, j)
+ *   in fp32, each operation rounded once (no fused multiply-add) and the max
+ *   not clamped at 0; the largest v_i is selected, exact ties going to the
+ *   lower candidate index i;
+ *   selection stops after min(k, valid candidates) steps.
+ * Results come out in SELECTION order, not score order; each carries its
+ * original relevance score s_i and its global row. A list of result keys is
+ * therefore NOT a valid input for vs_merge_keys (its lists are sorted
+ * descending), nor for a second vs_mmr_keys pass.
+ *  - d = 0 yields exactly the first k of vs_search, bit for bit (vs_search_mmr
+ *    then answers from the search for k itself and skips the selection;
+ *    vs_mmr_keys returns the first k keys of each list); d = 1 is pure
+ *    farthest-first selection from c_0.
+ *  - 1 <= k <= candidates_limit <= VS_MMR_MAX_CANDIDATES (the batched MFMA
+ *    candidate search's largest k, so a batch's candidate search stays on
+ *    those passes). candidates_limit == 0 means min(max(4 k, k), 128).
+ *    `diversity` outside [0, 1], or NaN, is VS_ERR_INVALID_ARG.
+ *  - The collection's rows must be whole 8-byte words (bf16: dim % 4 == 0,
+ *    fp32: dim % 2 == 0, as vs_checksum asks), else VS_ERR_INVALID_ARG.
+ *  - out_count[i] = min(k, valid candidates) (fewer rows, or fewer allowed
+ *    rows, than k); the outputs keep stride k, zero past the count.
+ *  - Supported on vs_open engines and on placed collections
+ *    (VS_FLAG_PLACE_COLLECTIONS; the call goes to the home device). A
+ *    row-striped collection keeps its candidates' rows on several devices:
+ *    both calls return VS_ERR_INVALID_ARG there. This limit is deliberate.
+ *  - A search: it takes the collection's reader lock across the candidate
+ *    search and the selection, so a vs_delete or vs_upsert never moves a
+ *    candidate's row between the two. */
+#define VS_MMR_MAX_CANDIDATES 128u
+int vs_search_mmr(vs_engine* eng, const char* coll, const float* queries, uint32_t nq,
+                  uint32_t dim, uint32_t k, uint32_t candidates_limit, float diversity,
+                  uint64_t filter_id, float* out_scores, uint64_t* out_rows,
+                  uint32_t* out_count);
+/* Device-pointer form: the selection stage alone. d_cand_keys is [nq][n_cand]
+ * candidate lists in the form vs_search_keys writes (sorted descending,
+ * 0-padded; 1 <= k <= n_cand <= VS_MMR_MAX_CANDIDATES), d_out_keys [nq][k]
+ * receives the selected keys in selection order, 0-padded; the two must not
+ * overlap. A key of 0, or one whose row is not a row of the collection, is an
+ * empty slot. Ordered on `stream` as vs_search_keys is, under the same
+ * one-runtime rule (vs_runtime_check). */
+int vs_mmr_keys(vs_engine* eng, const char* coll, const uint64_t* d_cand_keys, uint32_t nq,
+                uint32_t n_cand, uint32_t k, float diversity, uint64_t* d_out_keys,
+                void* stream);
 
 /* Merges `n_lists` per-shard key lists into the global top-k on the device:
  * d_lists is [n_lists][nq][k_in] (e.g. the result of an all-gather of

@@ -35,6 +35,22 @@
  * rows (its pairs are then lost), the collection is emptied on both sides and
  * the 500 says so: its ids could no longer be matched to rows.
  *
+ * /search takes one field outside the reference's four: an optional
+ * "mmr": {"diversity": number, "candidates_limit": integer} (Qdrant's
+ * query-API mmr object; include/vsearch.h "MMR search"). Both fields are
+ * optional (defaults 0.5 and 0 = the engine's min(4 top_k, 128)); a null
+ * "mmr", like its absence, leaves the route exactly as the reference's. An
+ * "mmr" that is not an object, a field of the wrong type, a diversity outside
+ * [0, 1] or a candidates_limit outside [0, 128] is 400 "Invalid request body".
+ * With it, top_k is clamped to the collection's rows as always and must then
+ * be at most 128 (else 400), candidates_limit is raised to at least that, and
+ * the request goes straight to vs_search_mmr with one query (not through the
+ * batcher), under the resident filter when "filter":"match" is configured and
+ * a filter is given (500 with the engine's message if it could not be made
+ * resident). The reply has the same shape, results in SELECTION order, each
+ * with its relevance score. 501 when the engine library has no vs_search_mmr
+ * (referenced weakly, as vs_delete).
+ *
  * Point UUIDs and payloads live here (a UUID -> row map and a row-indexed
  * payload store per collection); the engine sees dense rows only. A Go
  * deployment binds the same engine C-ABI through cgo and
