@@ -5,6 +5,7 @@ import (
 	"errors"
 	"fmt"
 	"log"
+	"math"
 	"net/http"
 	"reflect"
 	"sort"
@@ -322,6 +323,9 @@ type searchBody struct {
 	TopK       int                    `json:"top_k"`
 	Filter     map[string]interface{} `json:"filter"` // accepted, not applied (main.go:30)
 	MMR        *mmrBody               `json:"mmr"`    // an extension: Qdrant's query-API mmr object
+	// an extension: Qdrant's SearchGroups (include/vsearch_service.h)
+	GroupBy   *string `json:"group_by"`
+	GroupSize *int    `json:"group_size"` // default 1: the best chunk per document
 }
 
 // mmrBody is /search's optional "mmr" object (include/vsearch_service.h): both
@@ -340,6 +344,76 @@ type hit struct {
 type searchReply struct {
 	Results []hit `json:"results"`
 	Count   int   `json:"count"`
+}
+
+// groupedReply is /search's reply with "group_by": results flat in group
+// order (a group's hits adjacent), groups in the same order.
+type groupedReply struct {
+	Results []hit       `json:"results"`
+	Count   int         `json:"count"`
+	Groups  []groupInfo `json:"groups"`
+}
+
+type groupInfo struct {
+	ID   interface{} `json:"id"` // the payload value, as given
+	Hits int         `json:"hits"`
+}
+
+// groupKey is the group of a payload value: strings and integers are groups
+// (Qdrant's keyword and integer group keys), anything else is none.
+func groupKey(v interface{}) (string, bool) {
+	switch x := v.(type) {
+	case string:
+		return "s" + x, true
+	case float64: // encoding/json's number
+		if x == math.Trunc(x) && math.Abs(x) < 1<<63 {
+			return fmt.Sprintf("i%d", int64(x)), true
+		}
+	}
+	return "", false
+}
+
+// groupingFor returns the store's current grouping by payload key `key`,
+// building it (and letting stale ones go) when needed. Reader lock held.
+func (s *service) groupingFor(coll string, st *pointStore, key string) (*grouping, error) {
+	st.gmu.Lock()
+	defer st.gmu.Unlock()
+	if g, ok := st.groupings[key]; ok && g.version == st.version {
+		return g, nil
+	}
+	for k, g := range st.groupings { // stale ones serve nobody: searches hold the reader lock
+		if g.version != st.version {
+			_ = s.eng.GroupingDrop(g.id) // gone already after a delete
+			delete(st.groupings, k)
+		}
+	}
+	g := &grouping{version: st.version}
+	dense := map[string]uint32{}
+	gor := make([]uint32, len(st.payloads))
+	for r, pl := range st.payloads {
+		gor[r] = vsearch.GroupNone
+		if v, ok := pl[key]; ok {
+			if k, ok := groupKey(v); ok {
+				id, seen := dense[k]
+				if !seen {
+					id = uint32(len(g.values))
+					dense[k] = id
+					g.values = append(g.values, v)
+				}
+				gor[r] = id
+			}
+		}
+	}
+	id, err := s.eng.GroupingCreate(coll, gor, uint32(len(g.values)))
+	if err != nil {
+		return nil, err
+	}
+	g.id = id
+	if st.groupings == nil {
+		st.groupings = map[string]*grouping{}
+	}
+	st.groupings[key] = g
+	return g, nil
 }
 
 func (s *service) search(w http.ResponseWriter, r *http.Request) {
@@ -376,6 +450,18 @@ func (s *service) search(w http.ResponseWriter, r *http.Request) {
 			candidates = uint32(*m.CandidatesLimit)
 		}
 	}
+	groupSize := 1
+	if body.GroupSize != nil {
+		if *body.GroupSize < 1 || *body.GroupSize > int(vsearch.GroupsMaxSize) {
+			writeError(w, http.StatusBadRequest, "Invalid request body")
+			return
+		}
+		groupSize = *body.GroupSize
+	}
+	if body.GroupBy != nil && body.MMR != nil {
+		writeError(w, http.StatusBadRequest, "Invalid request body")
+		return
+	}
 	log.Printf("Searching in collection: %s, TopK: %d", body.Collection, body.TopK)
 	st := s.store(body.Collection)
 	if st == nil {
@@ -388,6 +474,10 @@ func (s *service) search(w http.ResponseWriter, r *http.Request) {
 	if uint32(len(body.Query)) != s.dim {
 		writeError(w, http.StatusInternalServerError, fmt.Sprintf(
 			"Search failed: Vector dimension error: expected dim: %d, got %d", s.dim, len(body.Query)))
+		return
+	}
+	if body.GroupBy != nil {
+		s.searchGroups(w, &body, st, groupSize)
 		return
 	}
 	reply := searchReply{Results: make([]hit, 0)}
@@ -427,6 +517,49 @@ func (s *service) search(w http.ResponseWriter, r *http.Request) {
 			}
 			reply.Results = append(reply.Results, hit{ID: st.ids[row],
 				Score: float64(hits.Scores[i]), Payload: pl})
+		}
+	}
+	reply.Count = len(reply.Results)
+	writeJSON(w, http.StatusOK, reply)
+}
+
+// searchGroups answers a /search carrying "group_by": one SearchGroups call
+// per request, past the batcher. The store's reader lock is held.
+func (s *service) searchGroups(w http.ResponseWriter, body *searchBody, st *pointStore,
+	groupSize int) {
+	reply := groupedReply{Results: make([]hit, 0), Groups: make([]groupInfo, 0)}
+	k := body.TopK
+	if rows := len(st.ids); k > rows && rows > 0 {
+		k = rows
+	}
+	if k > int(vsearch.GroupsMaxLimit) {
+		writeError(w, http.StatusBadRequest, fmt.Sprintf(
+			"top_k must not exceed %d with group_by", vsearch.GroupsMaxLimit))
+		return
+	}
+	if len(st.ids) > 0 {
+		g, err := s.groupingFor(body.Collection, st, *body.GroupBy)
+		if err != nil {
+			writeError(w, http.StatusInternalServerError, "Search failed: "+err.Error())
+			return
+		}
+		res, err := s.eng.SearchGroups(body.Collection, body.Query, s.dim, uint32(k),
+			uint32(groupSize), g.id, 0)
+		if err != nil {
+			writeError(w, http.StatusInternalServerError, "Search failed: "+err.Error())
+			return
+		}
+		for _, grp := range res[0] {
+			for i, row := range grp.Hits.Rows {
+				pl := st.payloads[row]
+				if pl == nil {
+					pl = map[string]interface{}{}
+				}
+				reply.Results = append(reply.Results, hit{ID: st.ids[row],
+					Score: float64(grp.Hits.Scores[i]), Payload: pl})
+			}
+			reply.Groups = append(reply.Groups, groupInfo{ID: g.values[grp.ID],
+				Hits: len(grp.Hits.Rows)})
 		}
 	}
 	reply.Count = len(reply.Results)

@@ -18,6 +18,18 @@ type pointStore struct {
 	rowOf    map[string]uint64
 	ids      []string
 	payloads []map[string]interface{}
+	// groupings ("group_by"), cached per payload key; one is current while its
+	// version is the store's, which every upsert, delete and load moves on
+	version   uint64
+	gmu       sync.Mutex
+	groupings map[string]*grouping
+}
+
+// grouping is the device-resident grouping of a collection by one payload key.
+type grouping struct {
+	version uint64
+	id      uint64        // vsearch.Engine.GroupingCreate's id
+	values  []interface{} // dense group id -> the payload value, first-seen row order
 }
 
 func newPointStore() *pointStore { return &pointStore{rowOf: map[string]uint64{}} }
@@ -92,6 +104,7 @@ func (p *pointStore) commit(ids []string, rows []uint64, payloads []map[string]i
 		p.ids[r] = ids[i]
 		p.payloads[r] = payloads[i]
 	}
+	p.version++
 }
 
 // remove renumbers the store after the engine deleted `rows` (distinct) and
@@ -108,6 +121,7 @@ func (p *pointStore) remove(rows, from, to []uint64) {
 	}
 	n := len(p.ids) - len(rows)
 	p.ids, p.payloads = p.ids[:n], p.payloads[:n]
+	p.version++
 }
 
 // sidecar is the store's snapshot next to the engine's rows.
@@ -155,6 +169,7 @@ func (p *pointStore) load(path string) error {
 	}
 	p.mu.Lock()
 	p.rowOf, p.ids, p.payloads = rowOf, sc.IDs, sc.Payloads
+	p.version++
 	p.mu.Unlock()
 	return nil
 }

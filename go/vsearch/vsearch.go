@@ -86,6 +86,23 @@ static int vsg_mmr_keys(vs_engine* h, const char* n, const uint64_t* ck, uint32_
                         uint32_t k, float div, uint64_t* o, void* st, vsg_err* e) {
 	return vsg_fin(vs_mmr_keys(h, n, ck, nq, nc, k, div, o, st), e);
 }
+static int vsg_grouping_create(vs_engine* h, const char* n, const uint32_t* g, uint64_t rows,
+                               uint32_t ng, uint64_t* id, vsg_err* e) {
+	return vsg_fin(vs_grouping_create(h, n, g, rows, ng, id), e);
+}
+static int vsg_grouping_drop(vs_engine* h, uint64_t id, vsg_err* e) {
+	return vsg_fin(vs_grouping_drop(h, id), e);
+}
+static int vsg_search_groups(vs_engine* h, const char* n, const float* q, uint32_t nq, uint32_t d,
+                             uint32_t limit, uint32_t size, uint64_t gid, uint64_t fid, uint32_t* og,
+                             uint32_t* oh, float* s, uint64_t* r, uint32_t* c, vsg_err* e) {
+	return vsg_fin(vs_search_groups(h, n, q, nq, d, limit, size, gid, fid, og, oh, s, r, c), e);
+}
+static int vsg_group_keys(vs_engine* h, const char* n, const float* q, uint32_t nq, uint32_t d,
+                          uint32_t limit, uint32_t size, uint64_t gid, uint64_t fid, uint64_t* k,
+                          uint32_t* g, void* st, vsg_err* e) {
+	return vsg_fin(vs_group_keys(h, n, q, nq, d, limit, size, gid, fid, k, g, st), e);
+}
 static int vsg_filter_create(vs_engine* h, const char* n, const uint64_t* a, uint64_t aw,
                              uint64_t* id, vsg_err* e) {
 	return vsg_fin(vs_filter_create(h, n, a, aw, id), e);
@@ -513,6 +530,105 @@ func (e *Engine) MMRKeys(name string, dCand, dOut unsafe.Pointer, nq, nCand, k u
 	var ce C.vsg_err
 	return check(C.vsg_mmr_keys(e.h, cs, (*C.uint64_t)(dCand), C.uint32_t(nq), C.uint32_t(nCand),
 		C.uint32_t(k), C.float(diversity), (*C.uint64_t)(dOut), stream, &ce), &ce)
+}
+
+// Limits and the "no group" id of grouped search (include/vsearch.h).
+const (
+	GroupNone      = uint32(C.VS_GROUP_NONE)
+	GroupsMaxLimit = uint32(C.VS_GROUPS_MAX_LIMIT)
+	GroupsMaxSize  = uint32(C.VS_GROUPS_MAX_SIZE)
+)
+
+// Group is one group of a grouped answer: its id in the grouping and its best
+// rows, best first.
+type Group struct {
+	ID   uint32
+	Hits Hits
+}
+
+// GroupingCreate makes a device-resident grouping of a collection
+// (vs_grouping_create): groupOfRow[r] < nGroups is row r's group, GroupNone
+// means none. It is bound to the collection's rows as a filter is: an append
+// makes it stale, Delete and DropCollection drop it.
+func (e *Engine) GroupingCreate(name string, groupOfRow []uint32, nGroups uint32) (uint64, error) {
+	cs := C.CString(name)
+	defer C.free(unsafe.Pointer(cs))
+	var p *C.uint32_t
+	if len(groupOfRow) > 0 {
+		p = (*C.uint32_t)(unsafe.Pointer(&groupOfRow[0]))
+	}
+	var id C.uint64_t
+	var ce C.vsg_err
+	rc := C.vsg_grouping_create(e.h, cs, p, C.uint64_t(len(groupOfRow)), C.uint32_t(nGroups), &id, &ce)
+	if err := check(rc, &ce); err != nil {
+		return 0, err
+	}
+	return uint64(id), nil
+}
+
+// GroupingDrop releases a grouping (vs_grouping_drop).
+func (e *Engine) GroupingDrop(id uint64) error {
+	var ce C.vsg_err
+	return check(C.vsg_grouping_drop(e.h, C.uint64_t(id), &ce), &ce)
+}
+
+// SearchGroups returns, per query, the best `limit` groups of the grouping and
+// the best `groupSize` rows of each (vs_search_groups; Qdrant's SearchGroups):
+// exact, best group first. filterID (0 = none) is a filter made by
+// FilterCreate. The reference's retrieval service regroups hits by
+// document_id on the host (rag/retrieval-service/main.go:264-333).
+func (e *Engine) SearchGroups(name string, queries []float32, dim, limit, groupSize uint32,
+	groupingID, filterID uint64) ([][]Group, error) {
+	if dim == 0 || len(queries) == 0 || len(queries)%int(dim) != 0 {
+		return nil, fmt.Errorf("vsearch: %d floats are not whole queries of dim %d: %w",
+			len(queries), dim, ErrInvalidArg)
+	}
+	if limit == 0 || limit > GroupsMaxLimit || groupSize == 0 || groupSize > GroupsMaxSize {
+		return nil, fmt.Errorf("vsearch: limit %d / group size %d out of range: %w", limit,
+			groupSize, ErrInvalidArg)
+	}
+	nq := len(queries) / int(dim)
+	cs := C.CString(name)
+	defer C.free(unsafe.Pointer(cs))
+	L, S := int(limit), int(groupSize)
+	groups := make([]uint32, nq*L)
+	nhits := make([]uint32, nq*L)
+	rows := make([]uint64, nq*L*S)
+	scores := make([]float32, nq*L*S)
+	count := make([]uint32, nq)
+	var ce C.vsg_err
+	rc := C.vsg_search_groups(e.h, cs, (*C.float)(unsafe.Pointer(&queries[0])), C.uint32_t(nq),
+		C.uint32_t(dim), C.uint32_t(limit), C.uint32_t(groupSize), C.uint64_t(groupingID),
+		C.uint64_t(filterID), (*C.uint32_t)(unsafe.Pointer(&groups[0])),
+		(*C.uint32_t)(unsafe.Pointer(&nhits[0])), (*C.float)(unsafe.Pointer(&scores[0])),
+		(*C.uint64_t)(unsafe.Pointer(&rows[0])), (*C.uint32_t)(unsafe.Pointer(&count[0])), &ce)
+	if err := check(rc, &ce); err != nil {
+		return nil, err
+	}
+	out := make([][]Group, nq)
+	for i := range out {
+		out[i] = make([]Group, count[i])
+		for j := range out[i] {
+			g := i*L + j
+			lo, n := g*S, int(nhits[g])
+			out[i][j] = Group{ID: groups[g], Hits: Hits{Rows: rows[lo : lo+n], Scores: scores[lo : lo+n]}}
+		}
+	}
+	return out, nil
+}
+
+// GroupKeys is the device-pointer form (vs_group_keys): dQueries holds
+// [nq][dim] fp32, dKeys receives [nq][limit][groupSize] result keys (0-padded),
+// dGroups [nq][limit] group ids (GroupNone past the count), all on `stream`
+// (a hipStream_t; nil = the null stream).
+func (e *Engine) GroupKeys(name string, dQueries unsafe.Pointer, nq, dim, limit, groupSize uint32,
+	groupingID, filterID uint64, dKeys, dGroups, stream unsafe.Pointer) error {
+	cs := C.CString(name)
+	defer C.free(unsafe.Pointer(cs))
+	var ce C.vsg_err
+	return check(C.vsg_group_keys(e.h, cs, (*C.float)(dQueries), C.uint32_t(nq), C.uint32_t(dim),
+		C.uint32_t(limit), C.uint32_t(groupSize), C.uint64_t(groupingID), C.uint64_t(filterID),
+		(*C.uint64_t)(dKeys), (*C.uint32_t)(dGroups), stream, &ce), &ce)
 }
 
 // Snapshot writes a collection's stored rows to path (replaces Qdrant's

@@ -35,6 +35,9 @@ KPROBE_LIB = os.path.join(HERE, "lib", "libvs_kprobe.so")
 # the int8 pass with its run_if word (tests/test_q8_split_wg_gpu.py), a shim of its own
 KPROBE_RUNIF_SRC = os.path.join(ROOT, "tests", "kprobe", "vs_kprobe_runif.cpp")
 KPROBE_RUNIF_LIB = os.path.join(HERE, "lib", "libvs_kprobe_runif.so")
+# the grouped-search stages (tests/test_groups_stages_gpu.py), a shim of its own
+KPROBE_GROUPS_SRC = os.path.join(ROOT, "tests", "kprobe", "vs_kprobe_groups.cpp")
+KPROBE_GROUPS_LIB = os.path.join(HERE, "lib", "libvs_kprobe_groups.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("VS_OFFLOAD_ARCH", "gfx950")
 
@@ -44,6 +47,7 @@ SOURCES = {
     "vs_q8.o": (["vs_q8.hip"], ["--offload-arch=" + ARCH, "-O3"]),
     "vs_delete.o": (["vs_delete.hip"], ["--offload-arch=" + ARCH, "-O3"]),
     "vs_mmr.o": (["vs_mmr.hip"], ["--offload-arch=" + ARCH, "-O3"]),
+    "vs_group.o": (["vs_group.hip"], ["--offload-arch=" + ARCH, "-O3"]),
     "vs_engine.o": (["vs_engine.cpp"], ["-O2", "-Wall"]),
     "vs_api.o": (["vs_api.cpp"], ["-O2", "-Wall"]),
 }
@@ -154,6 +158,11 @@ def build(verbose: bool = False, force: bool = False) -> str:
                "-o", KPROBE_RUNIF_LIB, "-L" + os.path.dirname(LIB), "-lvsearch", "-Wl,-rpath,$ORIGIN",
                "-Wl,-soname,libvs_kprobe_runif.so"]
         _run_if_changed(KPROBE_RUNIF_LIB, [KPROBE_RUNIF_SRC, LIB] + hdrs, cmd, verbose, force)
+    if os.path.exists(KPROBE_GROUPS_SRC):
+        cmd = [HIPCC, "-std=c++17", "-fPIC", "-O2", "-Wall", "-shared", "-I" + CSRC, KPROBE_GROUPS_SRC,
+               "-o", KPROBE_GROUPS_LIB, "-L" + os.path.dirname(LIB), "-lvsearch", "-Wl,-rpath,$ORIGIN",
+               "-Wl,-soname,libvs_kprobe_groups.so"]
+        _run_if_changed(KPROBE_GROUPS_LIB, [KPROBE_GROUPS_SRC, LIB] + hdrs, cmd, verbose, force)
     return LIB
 
 

@@ -35,8 +35,32 @@ extern "C" int vs_search_mmr(vs_engine* eng, const char* coll, const float* quer
                              uint32_t dim, uint32_t k, uint32_t candidates_limit, float diversity,
                              uint64_t filter_id, float* out_scores, uint64_t* out_rows,
                              uint32_t* out_count) __attribute__((weak));
+// ... and the grouped search: without it a /search carrying "group_by" answers 501.
+extern "C" int vs_grouping_create(vs_engine* eng, const char* coll, const uint32_t* group_of_row,
+                                  uint64_t n_rows, uint32_t n_groups, uint64_t* grouping_id)
+    __attribute__((weak));
+extern "C" int vs_grouping_drop(vs_engine* eng, uint64_t grouping_id) __attribute__((weak));
+extern "C" int vs_search_groups(vs_engine* eng, const char* coll, const float* queries,
+                                uint32_t nq, uint32_t dim, uint32_t limit, uint32_t group_size,
+                                uint64_t grouping_id, uint64_t filter_id, uint32_t* out_groups,
+                                uint32_t* out_hits, float* out_scores, uint64_t* out_rows,
+                                uint32_t* out_count) __attribute__((weak));
 
 namespace {
+
+// A device-resident grouping of one collection by one payload key ("group_by").
+// A request holds its reference while it searches; the device copy goes with
+// the last reference, so evicting an entry never pulls it from under a search.
+struct GroupEntry {
+  vs_engine* eng = nullptr;
+  uint64_t version = 0;    // CollState::version it was built at
+  uint64_t device_id = 0;  // vs_grouping_create's id
+  std::vector<Json> ids;   // dense group id -> the payload value, first-seen row order
+  ~GroupEntry() {
+    // gone already when a /delete or a drop of the collection took it
+    if (device_id && vs_grouping_drop) (void)vs_grouping_drop(eng, device_id);
+  }
+};
 
 struct CollState {
   std::string name;
@@ -64,6 +88,9 @@ struct CollState {
     uint64_t device_id = 0;  // 0: not resident (the mask is sent per call)
   };
   std::unordered_map<std::string, FilterEntry> fcache;
+  // groupings ("group_by"), cached per payload key under fmu and, like the
+  // filters, stale once `version` moves on; rebuilt at the next use
+  std::unordered_map<std::string, std::shared_ptr<GroupEntry>> gcache;
 };
 
 // Synthetic UUID of bulk row r: version 4, variant 10, the collection's
@@ -217,6 +244,11 @@ struct SearchRequest {  // main.go:26-31
   bool has_mmr = false;
   float mmr_diversity = 0.5f;
   uint32_t mmr_candidates = 0;  // 0: the engine's default, min(4 k, 128)
+  // "group_by": "<payload key>", "group_size": integer (an extension: Qdrant's
+  // SearchGroups; include/vsearch.h "Grouped search")
+  bool has_group = false;
+  std::string group_by;
+  uint32_t group_size = 1;  // the best chunk per document
 };
 
 // A JSON number literal at b[i..) (the grammar json.Decoder accepts):
@@ -437,6 +469,30 @@ std::string decode_search_generic(const char* body, size_t len, SearchRequest* r
       first = "mmr: not an object";
     }
   }
+  // "group_by" (null: absent) and "group_size" (null: the default 1); a wrong
+  // type, a group_size outside [1, VS_GROUPS_MAX_SIZE] or group_by together
+  // with mmr is a decode error
+  if (const Json* g = root.field("group_by")) {
+    if (g->kind == Json::String) {
+      req->has_group = true;
+      req->group_by = g->str;
+    } else if (g->kind != Json::Null && first.empty()) {
+      first = "group_by: not a string";
+    }
+  }
+  if (const Json* g = root.field("group_size")) {
+    int64_t v;
+    if (g->kind == Json::Number) {
+      if (!vsjson::parse_int64(g->str, &v) || v < 1 || v > (int64_t)VS_GROUPS_MAX_SIZE) {
+        if (first.empty()) first = "group_size: not an integer in [1, 16]";
+      } else {
+        req->group_size = (uint32_t)v;
+      }
+    } else if (g->kind != Json::Null && first.empty()) {
+      first = "group_size: not a number";
+    }
+  }
+  if (req->has_group && req->has_mmr && first.empty()) first = "group_by: not allowed with mmr";
   return first;
 }
 
@@ -770,6 +826,120 @@ CollState::FilterEntry filter_mask(vs_engine* eng, const std::string& coll, Coll
   return e;
 }
 
+// The group of a point: payload[key] when it is a string or an integer
+// (Qdrant's keyword and integer group keys); *k names it across rows.
+bool group_value(const Json& payload, const std::string& key, const Json** v, std::string* k) {
+  *v = payload.kind == Json::Object ? payload.get(key) : nullptr;
+  if (!*v) return false;
+  if ((*v)->kind == Json::String) {
+    *k = "s" + (*v)->str;
+    return true;
+  }
+  int64_t i;
+  if ((*v)->kind == Json::Number && vsjson::parse_int64((*v)->str, &i)) {
+    *k = "i" + std::to_string(i);
+    return true;
+  }
+  return false;
+}
+
+// The resident grouping of cs by payload key `key` (reader lock held by the
+// caller; no bulk rows). Built under fmu, so one request builds and the others
+// of the same collection wait for it. nullptr with *err when the engine refuses.
+std::shared_ptr<GroupEntry> grouping_for(vs_engine* eng, const std::string& coll, CollState& cs,
+                                         const std::string& key, std::string* err) {
+  std::lock_guard<std::mutex> g(cs.fmu);
+  auto it = cs.gcache.find(key);
+  if (it != cs.gcache.end() && it->second->version == cs.version) return it->second;
+  // entries of earlier versions serve nobody: every search in flight holds the
+  // reader lock, hence sees this version
+  for (auto i = cs.gcache.begin(); i != cs.gcache.end();)
+    i = i->second->version != cs.version ? cs.gcache.erase(i) : std::next(i);
+  if (cs.gcache.size() >= 16) cs.gcache.clear();  // held references keep theirs alive
+  const uint64_t n = cs.payload_of.size();
+  std::vector<uint32_t> gor(n, VS_GROUP_NONE);
+  auto e = std::make_shared<GroupEntry>();
+  std::unordered_map<std::string, uint32_t> dense;
+  std::string k;
+  const Json* v;
+  for (uint64_t r = 0; r < n; ++r)
+    if (group_value(cs.payload_of[r], key, &v, &k)) {
+      auto ins = dense.emplace(k, (uint32_t)e->ids.size());
+      if (ins.second) e->ids.push_back(*v);
+      gor[r] = ins.first->second;
+    }
+  uint64_t id = 0;
+  if (vs_grouping_create(eng, coll.c_str(), gor.data(), n, (uint32_t)e->ids.size(), &id) != VS_OK) {
+    *err = last_error();
+    if (err->empty()) *err = "the grouping could not be made resident";
+    return nullptr;
+  }
+  e->eng = eng;
+  e->version = cs.version;
+  e->device_id = id;
+  cs.gcache[key] = e;
+  return e;
+}
+
+// /search with "group_by": vs_search_groups with one query, past the batcher.
+// cs's reader lock is held; k = the clamped top_k = the number of groups.
+Response search_groups(vsvc* svc, const SearchRequest& req, CollState& cs, uint64_t k) {
+  if (k > VS_GROUPS_MAX_LIMIT)
+    return error_json("top_k must not exceed " + std::to_string(VS_GROUPS_MAX_LIMIT) +
+                          " with group_by",
+                      400);
+  // bulk-generated points have no payloads to group by
+  if (cs.bulk) return error_json("collection holds bulk-generated points", 400);
+  std::string err;
+  uint64_t fid = 0;
+  if (svc->filter_match && req.filter.kind == Json::Object && !req.filter.obj.empty()) {
+    fid = filter_mask(svc->eng, req.collection, cs, req.filter).device_id;
+    if (!fid) {  // vs_search_groups takes a resident filter only
+      err = last_error();
+      if (err.empty()) err = "the filter could not be made resident";
+      return error_json("Search failed: " + grpc_error(VS_ERR_INTERNAL, err), 500);
+    }
+  }
+  auto ge = grouping_for(svc->eng, req.collection, cs, req.group_by, &err);
+  if (!ge) return error_json("Search failed: " + grpc_error(VS_ERR_INTERNAL, err), 500);
+  const uint32_t S = req.group_size;
+  std::vector<uint32_t> groups(k), hits(k);
+  std::vector<float> scores(k * S);
+  std::vector<uint64_t> rows(k * S);
+  uint32_t count = 0;
+  const int rc = vs_search_groups(svc->eng, req.collection.c_str(), req.query.data(), 1, cs.dim,
+                                  (uint32_t)k, S, ge->device_id, fid, groups.data(), hits.data(),
+                                  scores.data(), rows.data(), &count);
+  if (rc != VS_OK) return error_json("Search failed: " + grpc_error(rc, last_error()), 500);
+  // results: flat, in group order, a group's hits adjacent (the retrieval
+  // service's decoder reads it unchanged); groups: the same order
+  std::string out, gs;
+  uint64_t total = 0;
+  out.append("{\"results\":[");
+  for (uint32_t j = 0; j < count; ++j) {
+    for (uint32_t h = 0; h < hits[j]; ++h) {
+      if (total++) out.push_back(',');
+      const uint64_t row = rows[(size_t)j * S + h];
+      out.append("{\"id\":");
+      vsjson::encode_string(uuid_at(cs, row), &out);
+      out.append(",\"score\":");
+      vsjson::encode_float64((double)scores[(size_t)j * S + h], &out);
+      out.append(",\"payload\":");
+      vsjson::encode(payload_at(cs, row), &out);
+      out.push_back('}');
+    }
+    if (j) gs.push_back(',');
+    gs.append("{\"id\":");
+    if (groups[j] < ge->ids.size()) vsjson::encode(ge->ids[groups[j]], &gs);
+    else gs.append("null");
+    gs.append(",\"hits\":" + std::to_string(hits[j]) + "}");
+  }
+  out.append("],\"count\":" + std::to_string(total) + ",\"groups\":[" + gs + "]}\n");
+  Response r;
+  r.body = std::move(out);
+  return r;
+}
+
 Response handle_search(vsvc* svc, const std::string& method, const char* body, size_t len) {
   if (method != "POST") return error_text("Method not allowed", 405);
   SearchRequest req;
@@ -782,6 +952,8 @@ Response handle_search(vsvc* svc, const std::string& method, const char* body, s
   const uint64_t limit = (uint64_t)req.top_k;  // Limit: uint64(req.TopK)
   if (req.has_mmr && !vs_search_mmr)
     return error_json("MMR search is not supported by this engine", 501);
+  if (req.has_group && !(vs_search_groups && vs_grouping_create && vs_grouping_drop))
+    return error_json("Grouped search is not supported by this engine", 501);
 
   auto cs = svc->find(req.collection);
   if (!cs) return error_json("Search failed: " + not_found(req.collection), 500);
@@ -792,6 +964,7 @@ Response handle_search(vsvc* svc, const std::string& method, const char* body, s
   // Qdrant returns min(limit, points): any limit is served (k > 1024 takes
   // the engine's large-k select), and buffers are sized by what can return
   uint64_t k = std::min<uint64_t>(limit, std::max<uint64_t>(rows, 1));
+  if (req.has_group) return search_groups(svc, req, *cs, k);
   std::vector<float> scores(k);
   std::vector<uint64_t> hit_rows(k);
   uint32_t count = 0;
@@ -941,6 +1114,7 @@ Response handle_delete(vsvc* svc, const std::string& method, const char* body, s
         ++cs->version;
         std::lock_guard<std::mutex> g(cs->fmu);
         cs->fcache.clear();
+        cs->gcache.clear();
         return error_json(msg + " (the collection was emptied)", 500);
       }
       return error_json(msg, 500);
@@ -958,6 +1132,7 @@ Response handle_delete(vsvc* svc, const std::string& method, const char* body, s
     for (auto& kv : cs->fcache)  // the engine dropped them with the delete
       if (kv.second.device_id) (void)vs_filter_drop(svc->eng, kv.second.device_id);
     cs->fcache.clear();
+    cs->gcache.clear();  // and its groupings
   }
   wl.unlock();
 
@@ -1094,7 +1269,15 @@ int vsvc_open(vs_engine* eng, const char* config_json, vsvc** out) {
   return VS_OK;
 }
 
-void vsvc_close(vsvc* svc) { delete svc; }  // the batcher drains and joins first
+void vsvc_close(vsvc* svc) {
+  if (!svc) return;
+  svc->batcher.reset();  // drains and joins first
+  // the engine frees its groupings with its collections: closing the service
+  // makes no engine call, so it is safe whichever of the two is closed first
+  for (auto& kv : svc->colls)
+    for (auto& g : kv.second->gcache) g.second->device_id = 0;
+  delete svc;
+}
 
 int vsvc_bulk_generate(vsvc* svc, const char* coll, uint64_t n, uint64_t seed) {
   if (!svc || !coll) return VS_ERR_INVALID_ARG;

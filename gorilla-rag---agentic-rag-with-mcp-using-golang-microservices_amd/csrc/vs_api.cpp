@@ -97,6 +97,10 @@ struct vs_engine {
   std::mutex filt_mu;
   std::unordered_map<uint64_t, SFilter> filters;
   uint64_t next_filter = 1;
+  // placed collections' groupings (guarded by filt_mu): dev_fid[0] is the id on
+  // the home device dev_idx[0]
+  std::unordered_map<uint64_t, SFilter> groupings;
+  uint64_t next_grouping = 1;
   // per-device scratch of the multi-shard search (guarded by that device
   // context's work_mu)
   struct Scratch {
@@ -566,6 +570,82 @@ int mmr_striped() {
               "live on several devices); use a vs_open engine or VS_FLAG_PLACE_COLLECTIONS");
 }
 
+int groups_striped() {
+  return fail(VS_ERR_INVALID_ARG,
+              "grouped search is not available on a row-striped collection (its rows' groups "
+              "live on several devices); use a vs_open engine or VS_FLAG_PLACE_COLLECTIONS");
+}
+
+// The home device's ids of a placed collection's grouping and filter (0: none).
+int placed_group_ids(vs_engine* E, const SColl& sc, uint64_t grouping_id, uint64_t filter_id,
+                     uint64_t* dev_gid, uint64_t* dev_fid) {
+  std::lock_guard<std::mutex> g(E->filt_mu);
+  auto ig = E->groupings.find(grouping_id);
+  if (ig == E->groupings.end())
+    return fail(VS_ERR_NOT_FOUND, "grouping " + std::to_string(grouping_id) + " not found");
+  if (ig->second.coll_gen != sc.gen)
+    return fail(VS_ERR_INVALID_ARG, "grouping " + std::to_string(grouping_id) +
+                                        " was built for another collection state");
+  *dev_gid = ig->second.dev_fid[0];
+  *dev_fid = 0;
+  if (filter_id) {
+    auto it = E->filters.find(filter_id);
+    if (it == E->filters.end())
+      return fail(VS_ERR_NOT_FOUND, "filter " + std::to_string(filter_id) + " not found");
+    if (it->second.coll_gen != sc.gen)
+      return fail(VS_ERR_INVALID_ARG, "filter " + std::to_string(filter_id) +
+                                          " was built for another collection state");
+    *dev_fid = it->second.dev_fid[0];
+  }
+  return VS_OK;
+}
+
+// vs_group_keys of a placed collection on device `home` != 0, as
+// placed_search_keys: the queries go to the home device, the stages run there
+// on its own stream, keys and group ids come back to dev 0; cs waits for them.
+int placed_group_keys(vs_engine* E, SColl& sc, const float* d_q, uint32_t nq, uint32_t limit,
+                      uint32_t group_size, uint64_t dev_gid, uint64_t dev_fid, uint64_t* d_keys,
+                      uint32_t* d_groups, hipStream_t cs) {
+  CtxSet& cx = *E->sets[0];
+  DevEngine* d0 = E->dev[0];
+  DevEngine* de = home_eng(E, sc);
+  auto& sd = cx.scr[sc.home];
+  auto c = vsd::find_coll(de, sc.iname[0].c_str());
+  if (!c) return not_found(sc.name.c_str());
+  std::shared_lock<std::shared_mutex> rl(c->mu);
+  std::shared_ptr<vsd::DevGrouping> dg;
+  std::shared_ptr<vsd::DevFilter> df;
+  if (const int rc = vsd::groups_lookup(de, *c, dev_gid, dev_fid, &dg, &df)) return rc;
+  const size_t qbytes = (size_t)nq * c->dim * 4;
+  const size_t kbytes = (size_t)nq * limit * group_size * 8, gbytes = (size_t)nq * limit * 4;
+  std::unique_lock<std::mutex> g0(d0->work_mu, std::defer_lock), gh(de->work_mu, std::defer_lock);
+  std::lock(g0, gh);
+  VS_HIP(vsd::set_dev(d0), "hipSetDevice");
+  VS_HIP(hipEventRecord(cx.scr[0].qev, cs), "query event");
+  VS_HIP(vsd::set_dev(de), "hipSetDevice");
+  VS_HIP(vsd::use_stream(de, de->own), "stream order");
+  if (sd.q.bytes < qbytes || sd.keys.bytes < kbytes || sd.gather.bytes < gbytes) {
+    VS_HIP(hipStreamSynchronize(de->stream), "sync");
+    VS_HIP(sd.q.ensure(qbytes), "alloc queries");
+    VS_HIP(sd.keys.ensure(kbytes), "alloc keys");
+    VS_HIP(sd.gather.ensure(gbytes), "alloc group ids");
+  }
+  VS_HIP(hipStreamWaitEvent(de->stream, cx.scr[0].qev, 0), "query order");
+  VS_HIP(hipMemcpyPeerAsync(sd.q.p, de->device, d_q, d0->device, qbytes, de->stream),
+         "query peer copy");
+  const int rc = vsd::groups_core(de, *c, sd.q.as<float>(), nq, limit, group_size, *dg, df.get(),
+                                  sd.keys.as<uint64_t>(), sd.gather.as<uint32_t>());
+  if (rc != VS_OK) return rc;
+  VS_HIP(hipMemcpyPeerAsync(d_keys, d0->device, sd.keys.p, de->device, kbytes, de->stream),
+         "keys peer copy");
+  VS_HIP(hipMemcpyPeerAsync(d_groups, d0->device, sd.gather.p, de->device, gbytes, de->stream),
+         "group ids peer copy");
+  VS_HIP(hipEventRecord(sd.kev, de->stream), "keys event");
+  VS_HIP(vsd::set_dev(d0), "hipSetDevice");
+  VS_HIP(hipStreamWaitEvent(cs, sd.kev, 0), "keys order");
+  return VS_OK;
+}
+
 // stored rows of a sharded collection, global rows [first, first + n), in
 // global order, through per-shard reads (fp32 widened, or raw stored bytes)
 template <bool RAW>
@@ -843,6 +923,8 @@ int sharded_drop(vs_engine* E, const char* name) {
     std::lock_guard<std::mutex> g(E->filt_mu);
     for (auto it = E->filters.begin(); it != E->filters.end();)
       it = it->second.coll_gen == sc->gen ? E->filters.erase(it) : std::next(it);
+    for (auto it = E->groupings.begin(); it != E->groupings.end();)
+      it = it->second.coll_gen == sc->gen ? E->groupings.erase(it) : std::next(it);
   }
   if (sc->home >= 0) {
     (void)vsd::collection_drop(home_eng(E, *sc), sc->iname[0].c_str());  // frees its filters
@@ -931,6 +1013,8 @@ int sharded_delete(vs_engine* E, const char* coll, uint64_t n, const uint64_t* r
     std::lock_guard<std::mutex> g(E->filt_mu);
     for (auto it = E->filters.begin(); it != E->filters.end();)
       it = it->second.coll_gen == sc->gen ? E->filters.erase(it) : std::next(it);
+    for (auto it = E->groupings.begin(); it != E->groupings.end();)
+      it = it->second.coll_gen == sc->gen ? E->groupings.erase(it) : std::next(it);
   };
   if (sc->home >= 0) {
     const int rc = vsd::delete_rows(home_eng(E, *sc), sc->iname[0].c_str(), n, rows, moved_from,
@@ -1486,6 +1570,95 @@ int vs_mmr_keys(vs_engine* eng, const char* coll, const uint64_t* d_cand_keys, u
                          d_out_keys, stream);
   return placed_mmr_keys(eng, *sc, d_cand_keys, nq, n_cand, k, diversity, d_out_keys,
                          (hipStream_t)stream);
+}
+
+int vs_grouping_create(vs_engine* eng, const char* coll, const uint32_t* group_of_row,
+                       uint64_t n_rows, uint32_t n_groups, uint64_t* grouping_id) {
+  if (!eng) return fail(VS_ERR_INVALID_ARG, "engine is NULL");
+  if (!eng->sharded)
+    return vsd::grouping_create(eng->dev[0], coll, group_of_row, n_rows, n_groups, grouping_id);
+  if (!grouping_id) return fail(VS_ERR_INVALID_ARG, "NULL argument");
+  auto sc = find_scoll(eng, coll);
+  if (!sc) return not_found(coll);
+  if (sc->home < 0) return groups_striped();
+  SFilter f;
+  f.coll_gen = sc->gen;
+  uint64_t id = 0;
+  const int rc = vsd::grouping_create(home_eng(eng, *sc), sc->iname[0].c_str(), group_of_row,
+                                      n_rows, n_groups, &id);
+  if (rc != VS_OK) return rc;
+  f.dev_fid.push_back(id);
+  f.dev_idx.push_back((uint32_t)sc->home);
+  std::lock_guard<std::mutex> g(eng->filt_mu);
+  *grouping_id = eng->next_grouping++;
+  eng->groupings.emplace(*grouping_id, std::move(f));
+  return VS_OK;
+}
+
+int vs_grouping_drop(vs_engine* eng, uint64_t grouping_id) {
+  if (!eng) return fail(VS_ERR_INVALID_ARG, "engine is NULL");
+  if (!eng->sharded) return vsd::grouping_drop(eng->dev[0], grouping_id);
+  SFilter f;
+  {
+    std::lock_guard<std::mutex> g(eng->filt_mu);
+    auto it = eng->groupings.find(grouping_id);
+    if (it == eng->groupings.end())
+      return fail(VS_ERR_NOT_FOUND, "grouping " + std::to_string(grouping_id) + " not found");
+    f = std::move(it->second);
+    eng->groupings.erase(it);
+  }
+  (void)vsd::grouping_drop(eng->dev[f.dev_idx[0]], f.dev_fid[0]);  // gone with its collection
+  return VS_OK;
+}
+
+int vs_search_groups(vs_engine* eng, const char* coll, const float* queries, uint32_t nq,
+                     uint32_t dim, uint32_t limit, uint32_t group_size, uint64_t grouping_id,
+                     uint64_t filter_id, uint32_t* out_groups, uint32_t* out_hits,
+                     float* out_scores, uint64_t* out_rows, uint32_t* out_count) {
+  if (!eng) return fail(VS_ERR_INVALID_ARG, "engine is NULL");
+  if (!eng->sharded)
+    return vsd::search_groups_host(eng->dev[0], coll, queries, nq, dim, limit, group_size,
+                                   grouping_id, filter_id, out_groups, out_hits, out_scores,
+                                   out_rows, out_count);
+  if (const int rc = vsd::groups_args(limit, group_size)) return rc;
+  if (nq == 0) return VS_OK;
+  if (!queries) return fail(VS_ERR_INVALID_ARG, "queries is NULL");
+  auto sc = find_scoll(eng, coll);
+  if (!sc) return not_found(coll);
+  if (sc->home < 0) return groups_striped();
+  uint64_t dev_gid = 0, dev_fid = 0;
+  if (const int rc = placed_group_ids(eng, *sc, grouping_id, filter_id, &dev_gid, &dev_fid))
+    return rc;
+  return vsd::search_groups_host(home_eng(eng, *sc), sc->iname[0].c_str(), queries, nq, dim, limit,
+                                 group_size, dev_gid, dev_fid, out_groups, out_hits, out_scores,
+                                 out_rows, out_count);
+}
+
+int vs_group_keys(vs_engine* eng, const char* coll, const float* d_queries, uint32_t nq,
+                  uint32_t dim, uint32_t limit, uint32_t group_size, uint64_t grouping_id,
+                  uint64_t filter_id, uint64_t* d_keys, uint32_t* d_groups, void* stream) {
+  if (!eng) return fail(VS_ERR_INVALID_ARG, "engine is NULL");
+  if (const int rt = vsd::one_hip_runtime()) return rt;
+  if (!eng->sharded)
+    return vsd::group_keys(eng->dev[0], coll, d_queries, nq, dim, limit, group_size, grouping_id,
+                           filter_id, d_keys, d_groups, stream);
+  if (const int rc = vsd::groups_args(limit, group_size)) return rc;
+  if (nq == 0) return VS_OK;
+  if (!d_queries || !d_keys || !d_groups) return fail(VS_ERR_INVALID_ARG, "NULL device pointer");
+  auto sc = find_scoll(eng, coll);
+  if (!sc) return not_found(coll);
+  if (sc->home < 0) return groups_striped();
+  if (dim != sc->dim)
+    return fail(VS_ERR_DIM_MISMATCH, "Vector dimension error: expected dim: " +
+                                         std::to_string(sc->dim) + ", got " + std::to_string(dim));
+  uint64_t dev_gid = 0, dev_fid = 0;
+  if (const int rc = placed_group_ids(eng, *sc, grouping_id, filter_id, &dev_gid, &dev_fid))
+    return rc;
+  if (sc->home == 0)
+    return vsd::group_keys(eng->dev[0], sc->iname[0].c_str(), d_queries, nq, dim, limit,
+                           group_size, dev_gid, dev_fid, d_keys, d_groups, stream);
+  return placed_group_keys(eng, *sc, d_queries, nq, limit, group_size, dev_gid, dev_fid, d_keys,
+                           d_groups, (hipStream_t)stream);
 }
 
 int vs_merge_keys(vs_engine* eng, const uint64_t* d_lists, uint32_t n_lists, uint32_t nq,

@@ -244,6 +244,15 @@ struct DevFilter {
   DevBuf bits, list;               // bitmap; compacted rows when selective
 };
 
+// A device-resident grouping (vs_grouping_create): one group id per local row.
+// Shared as a filter is: a search holds its reference until the device is done.
+struct DevGrouping {
+  uint64_t coll_gen = 0;  // Collection::gen it was built for
+  uint64_t rows = 0;      // collection rows it was built over
+  uint32_t n_groups = 0;
+  DevBuf gid;             // rows u32
+};
+
 struct DevEngine;
 
 // What the search contexts of one device share: the resident collections and
@@ -255,6 +264,8 @@ struct DevStore {
   std::mutex filt_mu;
   std::unordered_map<uint64_t, std::shared_ptr<DevFilter>> filters;
   uint64_t next_filter = 1;
+  std::unordered_map<uint64_t, std::shared_ptr<DevGrouping>> groupings;  // guarded by filt_mu
+  uint64_t next_grouping = 1;
   std::vector<DevEngine*> ctx;
 };
 
@@ -290,6 +301,9 @@ struct DevEngine {
   DevBuf small_part;
   DevBuf q8g;  // one query on the int8 copy: workgroup lists, wave bounds, candidates
   DevBuf mmr_cand;  // vs_search_mmr: the candidate search's keys, [nq][candidates_limit]
+  // grouped search: the groups' best keys (zero between calls), the workgroup
+  // lists, the returned heads, the answer's group ids [nq][limit]
+  DevBuf grp_best, grp_lists, grp_heads, grp_ids;
   DevBuf del;  // vs_delete: rows, bitmaps, the pair lists, the tile list, a striped delete's
                // staged rows; kept between calls up to 64 MiB, released above (delete_rows)
   // (r05) per collection (Collection::gen): what this context has answered
@@ -375,6 +389,28 @@ int mmr_keys(DevEngine* eng, const char* coll, const uint64_t* d_cand_keys, uint
 // reader lock held by the caller.
 int mmr_core(DevEngine* eng, Collection& c, const uint64_t* d_cand, uint32_t nq, uint32_t n_cand,
              uint32_t k, float diversity, uint64_t* d_out);
+// Grouped search (include/vsearch.h states the rule). groups_args checks limit
+// and group_size alone, so every layout reports them before the collection.
+int groups_args(uint32_t limit, uint32_t group_size);
+int grouping_create(DevEngine* eng, const char* coll, const uint32_t* group_of_row,
+                    uint64_t n_rows, uint32_t n_groups, uint64_t* grouping_id);
+int grouping_drop(DevEngine* eng, uint64_t grouping_id);
+int search_groups_host(DevEngine* eng, const char* coll, const float* queries, uint32_t nq,
+                       uint32_t dim, uint32_t limit, uint32_t group_size, uint64_t grouping_id,
+                       uint64_t filter_id, uint32_t* out_groups, uint32_t* out_hits,
+                       float* out_scores, uint64_t* out_rows, uint32_t* out_count);
+int group_keys(DevEngine* eng, const char* coll, const float* d_queries, uint32_t nq,
+               uint32_t dim, uint32_t limit, uint32_t group_size, uint64_t grouping_id,
+               uint64_t filter_id, uint64_t* d_keys, uint32_t* d_groups, void* stream);
+// The grouping and filter of a grouped search, checked against the collection's
+// state (its reader lock held); *df stays null when filter_id is 0.
+int groups_lookup(DevEngine* eng, const Collection& c, uint64_t grouping_id, uint64_t filter_id,
+                  std::shared_ptr<DevGrouping>* dg, std::shared_ptr<DevFilter>* df);
+// Query preprocessing and the stages on eng->stream for raw device queries;
+// work_mu and the collection's reader lock held by the caller.
+int groups_core(DevEngine* eng, Collection& c, const float* d_q, uint32_t nq, uint32_t limit,
+                uint32_t group_size, const DevGrouping& dg, const DevFilter* df, uint64_t* d_keys,
+                uint32_t* d_groups);
 int merge_keys(DevEngine* eng, const uint64_t* d_lists, uint32_t n_lists, uint32_t nq,
                uint32_t k_in, uint32_t k, uint64_t* d_out_keys, void* stream);
 // launch_merge for any k on eng->stream (k or k_in > vsk::kMaxK: the sort

@@ -1164,6 +1164,7 @@ void close(DevEngine* eng) {
   {
     std::lock_guard<std::mutex> g(st->filt_mu);
     st->filters.clear();
+    st->groupings.clear();
   }
   {
     std::lock_guard<std::mutex> g(st->map_mu);
@@ -1277,6 +1278,8 @@ int collection_drop(DevEngine* eng, const char* name) {
   std::lock_guard<std::mutex> gf(st.filt_mu);
   for (auto it = st.filters.begin(); it != st.filters.end();)
     it = it->second->coll_gen == c->gen ? st.filters.erase(it) : std::next(it);
+  for (auto it = st.groupings.begin(); it != st.groupings.end();)
+    it = it->second->coll_gen == c->gen ? st.groupings.erase(it) : std::next(it);
   return VS_OK;  // memory released with the last reference
 }
 
@@ -1587,6 +1590,8 @@ void delete_finish(DevEngine* eng, Collection& c, uint64_t new_rows, bool keep, 
   std::lock_guard<std::mutex> gf(st.filt_mu);
   for (auto it = st.filters.begin(); it != st.filters.end();)
     it = it->second->coll_gen == c.gen ? st.filters.erase(it) : std::next(it);
+  for (auto it = st.groupings.begin(); it != st.groupings.end();)
+    it = it->second->coll_gen == c.gen ? st.groupings.erase(it) : std::next(it);
 }
 
 // The delete scratch is kept between calls up to this size; a larger one (a
@@ -2336,6 +2341,311 @@ int mmr_keys(DevEngine* eng, const char* coll, const uint64_t* d_cand_keys, uint
   // call's writes to the rows among it)
   VS_HIP(use_stream(eng, (hipStream_t)stream), "stream order");
   return mmr_core(eng, *c, d_cand_keys, nq, n_cand, k, diversity, d_out_keys);
+}
+
+// ---- grouped search (include/vsearch.h "Grouped search") --------------------
+
+int groups_args(uint32_t limit, uint32_t group_size) {
+  if (limit == 0) return fail(VS_ERR_INVALID_ARG, "limit must be at least 1");
+  if (limit > VS_GROUPS_MAX_LIMIT)
+    return fail(VS_ERR_INVALID_ARG, "limit " + std::to_string(limit) +
+                                        " exceeds VS_GROUPS_MAX_LIMIT " +
+                                        std::to_string(VS_GROUPS_MAX_LIMIT));
+  if (group_size == 0) return fail(VS_ERR_INVALID_ARG, "group_size must be at least 1");
+  if (group_size > VS_GROUPS_MAX_SIZE)
+    return fail(VS_ERR_INVALID_ARG, "group_size " + std::to_string(group_size) +
+                                        " exceeds VS_GROUPS_MAX_SIZE " +
+                                        std::to_string(VS_GROUPS_MAX_SIZE));
+  return VS_OK;
+}
+
+int grouping_create(DevEngine* eng, const char* coll, const uint32_t* group_of_row,
+                    uint64_t n_rows, uint32_t n_groups, uint64_t* grouping_id) {
+  if (!eng || !grouping_id || (!group_of_row && n_rows))
+    return fail(VS_ERR_INVALID_ARG, "NULL argument");
+  auto c = find_coll(eng, coll);
+  if (!c) return fail(VS_ERR_NOT_FOUND, std::string("collection ") + (coll ? coll : "") +
+                                            " not found");
+  std::shared_lock<std::shared_mutex> rl(c->mu);
+  if (n_rows != c->rows)
+    return fail(VS_ERR_INVALID_ARG, "grouping has " + std::to_string(n_rows) +
+                                        " rows, the collection has " + std::to_string(c->rows));
+  if (c->rows >= 0xFFFFFFFFull) return fail(VS_ERR_INVALID_ARG, "collection exceeds 2^32-1 rows");
+  if (n_groups > std::max<uint64_t>(n_rows, 1))
+    return fail(VS_ERR_INVALID_ARG, "n_groups " + std::to_string(n_groups) +
+                                        " exceeds the collection's rows");
+  for (uint64_t r = 0; r < n_rows; ++r)
+    if (group_of_row[r] >= n_groups && group_of_row[r] != VS_GROUP_NONE)
+      return fail(VS_ERR_INVALID_ARG, "row " + std::to_string(r) + " has group " +
+                                          std::to_string(group_of_row[r]) + ", n_groups is " +
+                                          std::to_string(n_groups));
+  std::lock_guard<std::mutex> g(eng->work_mu);
+  VS_HIP(set_dev(eng), "hipSetDevice");
+  VS_HIP(use_stream(eng, eng->own), "stream order");
+  auto gr = std::make_shared<DevGrouping>();
+  gr->coll_gen = c->gen;
+  gr->rows = c->rows;
+  gr->n_groups = n_groups;
+  VS_HIP(gr->gid.ensure(std::max<uint64_t>(n_rows, 1) * 4), "alloc group ids");
+  if (n_rows)
+    VS_HIP(hipMemcpyAsync(gr->gid.p, group_of_row, n_rows * 4, hipMemcpyHostToDevice, eng->stream),
+           "group ids H2D");
+  VS_HIP(hipStreamSynchronize(eng->stream), "grouping sync");  // ready for every context
+  DevStore& st = *eng->store;
+  std::lock_guard<std::mutex> gf(st.filt_mu);
+  *grouping_id = st.next_grouping++;
+  st.groupings.emplace(*grouping_id, std::move(gr));
+  return VS_OK;
+}
+
+int grouping_drop(DevEngine* eng, uint64_t grouping_id) {
+  if (!eng) return fail(VS_ERR_INVALID_ARG, "engine is NULL");
+  std::shared_ptr<DevGrouping> gr;  // freed here unless a search still holds it
+  {
+    DevStore& st = *eng->store;
+    std::lock_guard<std::mutex> gf(st.filt_mu);
+    auto it = st.groupings.find(grouping_id);
+    if (it == st.groupings.end())
+      return fail(VS_ERR_NOT_FOUND, "grouping " + std::to_string(grouping_id) + " not found");
+    gr = std::move(it->second);
+    st.groupings.erase(it);
+  }
+  if (gr.use_count() == 1) {  // the primary's device-pointer searches may still read it
+    std::lock_guard<std::mutex> g(eng->work_mu);
+    VS_HIP(set_dev(eng), "hipSetDevice");
+    VS_HIP(hipStreamSynchronize(eng->stream), "sync");
+  }
+  return VS_OK;
+}
+
+int groups_lookup(DevEngine* eng, const Collection& c, uint64_t grouping_id, uint64_t filter_id,
+                  std::shared_ptr<DevGrouping>* dg, std::shared_ptr<DevFilter>* df) {
+  {
+    DevStore& st = *eng->store;
+    std::lock_guard<std::mutex> gf(st.filt_mu);
+    auto it = st.groupings.find(grouping_id);
+    if (it != st.groupings.end()) *dg = it->second;
+  }
+  if (!*dg) return fail(VS_ERR_NOT_FOUND, "grouping " + std::to_string(grouping_id) + " not found");
+  if ((*dg)->coll_gen != c.gen || (*dg)->rows != c.rows)
+    return fail(VS_ERR_INVALID_ARG, "grouping " + std::to_string(grouping_id) +
+                                        " was built for another collection state");
+  if (filter_id) {
+    *df = find_filter(eng, filter_id);
+    if (!*df) return fail(VS_ERR_NOT_FOUND, "filter " + std::to_string(filter_id) + " not found");
+    if ((*df)->coll_gen != c.gen || (*df)->rows != c.rows)
+      return fail(VS_ERR_INVALID_ARG, "filter " + std::to_string(filter_id) +
+                                          " was built for another collection state");
+  }
+  return VS_OK;
+}
+
+// Per query, as search_large_k: the score pass, then the group stages on its
+// images (vs_group.hip). The digit histogram the score pass counts into and the
+// groups' best keys are zero between calls and left zero.
+int groups_core(DevEngine* eng, Collection& c, const float* d_q, uint32_t nq, uint32_t limit,
+                uint32_t group_size, const DevGrouping& dg, const DevFilter* df, uint64_t* d_keys,
+                uint32_t* d_groups) {
+  const uint32_t T = limit * group_size;
+  if (c.rows == 0) {
+    VS_HIP(hipMemsetAsync(d_keys, 0, (size_t)nq * T * 8, eng->stream), "clear keys");
+    VS_HIP(hipMemsetAsync(d_groups, 0xFF, (size_t)nq * limit * 4, eng->stream), "clear groups");
+    return VS_OK;
+  }
+  if (c.rows >= 0xFFFFFFFFull || c.row_base + c.rows >= 0xFFFFFFFFull)
+    return fail(VS_ERR_INVALID_ARG, "collection exceeds 2^32-1 rows");
+  const uint32_t n_rows = (uint32_t)c.rows, dim = c.dim;
+  const bool bf16 = c.dtype == VS_DTYPE_BF16;
+  const uint32_t L = vsk::group_lists(n_rows);
+  // the preprocessed queries, padded as search_core keeps q_pre
+  const size_t qbytes = (size_t)((nq + vsk::kMfmaQueries - 1) / vsk::kMfmaQueries) *
+                        vsk::kMfmaQueries * dim * 4;
+  const size_t best_bytes = (size_t)std::max<uint32_t>(dg.n_groups, 1) * 8;
+  if (eng->q_pre.bytes < qbytes || eng->lk_sc.bytes < (size_t)n_rows * 4 ||
+      eng->lk_hist.bytes < vsk::kRselBins * 4 || eng->grp_best.bytes < best_bytes ||
+      eng->grp_lists.bytes < (size_t)L * T * 8 || eng->grp_heads.bytes < (size_t)limit * 8) {
+    VS_HIP(hipStreamSynchronize(eng->stream), "sync");
+    if (eng->q_pre.bytes < qbytes) {
+      VS_HIP(eng->q_pre.ensure(qbytes), "alloc query scratch");
+      VS_HIP(hipMemsetAsync(eng->q_pre.p, 0, eng->q_pre.bytes, eng->stream), "zero query scratch");
+    }
+    VS_HIP(eng->lk_sc.ensure((size_t)n_rows * 4), "alloc score images");
+    if (eng->lk_hist.bytes < vsk::kRselBins * 4) {
+      VS_HIP(eng->lk_hist.ensure(vsk::kRselBins * 4), "alloc digit histogram");
+      VS_HIP(hipMemsetAsync(eng->lk_hist.p, 0, eng->lk_hist.bytes, eng->stream), "zero");
+    }
+    if (eng->grp_best.bytes < best_bytes) {
+      VS_HIP(eng->grp_best.ensure(best_bytes), "alloc group bests");
+      VS_HIP(hipMemsetAsync(eng->grp_best.p, 0, eng->grp_best.bytes, eng->stream), "zero");
+    }
+    VS_HIP(eng->grp_lists.ensure((size_t)L * T * 8), "alloc group lists");
+    VS_HIP(eng->grp_heads.ensure((size_t)limit * 8), "alloc group heads");
+  }
+  float* qp = eng->q_pre.as<float>();
+  VS_HIP(vsk::launch_query_prep(d_q, nq, dim, c.metric == VS_METRIC_COSINE, bf16, qp, nullptr,
+                                eng->stream),
+         "query preprocess");
+  const uint64_t* allow = df ? df->bits.as<uint64_t>() : nullptr;
+  uint32_t* sc = eng->lk_sc.as<uint32_t>();
+  uint32_t* hist = eng->lk_hist.as<uint32_t>();
+  const uint32_t* gid = dg.gid.as<uint32_t>();
+  uint64_t* best = eng->grp_best.as<uint64_t>();
+  uint64_t* lists = eng->grp_lists.as<uint64_t>();
+  uint64_t* heads = eng->grp_heads.as<uint64_t>();
+  const uint32_t rb = (uint32_t)c.row_base;
+  for (uint32_t i = 0; i < nq; ++i) {
+    VS_HIP(ev_begin(eng, eng->scan_ev), "event");
+    VS_HIP(vsk::launch_gemv_scores(c.data, bf16, dim, n_rows, qp + (size_t)i * dim, allow, sc, hist,
+                                   eng->stream),
+           "score pass");
+    VS_HIP(ev_end(eng, eng->scan_ev), "event");
+    VS_HIP(ev_begin(eng, eng->merge_ev), "event");
+    VS_HIP(vsk::launch_group_best(sc, gid, n_rows, rb, dg.n_groups, best, hist, eng->stream),
+           "group best");
+    VS_HIP(vsk::launch_group_heads(sc, gid, best, n_rows, rb, dg.n_groups, limit, lists,
+                                   eng->stream),
+           "group heads");
+    VS_HIP(vsk::launch_merge(lists, L, limit, 0, 1, limit, limit, heads, eng->stream),
+           "merge heads");
+    VS_HIP(vsk::launch_group_members(sc, gid, best, n_rows, rb, dg.n_groups, heads, limit,
+                                     group_size, lists, d_groups + (size_t)i * limit, eng->stream),
+           "group members");
+    VS_HIP(vsk::launch_merge(lists, L, T, group_size, limit, group_size, group_size,
+                             d_keys + (size_t)i * T, eng->stream),
+           "merge members");
+    VS_HIP(vsk::launch_group_clear(best, dg.n_groups, eng->stream), "clear group bests");
+    VS_HIP(ev_end(eng, eng->merge_ev), "event");
+  }
+  return VS_OK;
+}
+
+// The answer's keys [nq][limit][S] and group ids [nq][limit] -> the caller's
+// arrays (any but count may be null), zero past the counts.
+static void decode_groups(const uint64_t* keys, const uint32_t* gids, uint32_t nq, uint32_t limit,
+                          uint32_t S, uint32_t* out_groups, uint32_t* out_hits, float* out_scores,
+                          uint64_t* out_rows, uint32_t* out_count) {
+  for (uint32_t i = 0; i < nq; ++i) {
+    uint32_t ng = 0;
+    for (uint32_t j = 0; j < limit; ++j) {
+      const size_t gj = (size_t)i * limit + j;
+      const bool on = gids[gj] != VS_GROUP_NONE;
+      uint32_t hits = 0;
+      for (uint32_t h = 0; h < S; ++h) {
+        const uint64_t key = on ? keys[gj * S + h] : 0ull;
+        if (key) ++hits;
+        if (out_scores) out_scores[gj * S + h] = key ? vs::key_score(key) : 0.f;
+        if (out_rows) out_rows[gj * S + h] = key ? vs::key_row(key) : 0;
+      }
+      if (out_groups) out_groups[gj] = on ? gids[gj] : 0;
+      if (out_hits) out_hits[gj] = hits;
+      ng += on ? 1u : 0u;
+    }
+    if (out_count) out_count[i] = ng;
+  }
+}
+
+// search_mmr_host's shape: the reader lock spans the whole call.
+int search_groups_host(DevEngine* eng, const char* coll, const float* queries, uint32_t nq,
+                       uint32_t dim, uint32_t limit, uint32_t group_size, uint64_t grouping_id,
+                       uint64_t filter_id, uint32_t* out_groups, uint32_t* out_hits,
+                       float* out_scores, uint64_t* out_rows, uint32_t* out_count) {
+  if (!eng) return fail(VS_ERR_INVALID_ARG, "engine is NULL");
+  const int arc = groups_args(limit, group_size);
+  if (arc != VS_OK) return arc;
+  if (nq == 0) return VS_OK;
+  if (!queries) return fail(VS_ERR_INVALID_ARG, "queries is NULL");
+  auto c = find_coll(eng, coll);
+  if (!c) return fail(VS_ERR_NOT_FOUND, std::string("collection ") + (coll ? coll : "") +
+                                            " not found");
+  if (dim != c->dim)
+    return fail(VS_ERR_DIM_MISMATCH, "Vector dimension error: expected dim: " +
+                                         std::to_string(c->dim) + ", got " + std::to_string(dim));
+  std::shared_lock<std::shared_mutex> rl(c->mu);
+  std::shared_ptr<DevGrouping> dg;
+  std::shared_ptr<DevFilter> df;
+  const int lrc = groups_lookup(eng, *c, grouping_id, filter_id, &dg, &df);
+  if (lrc != VS_OK) return lrc;
+  std::unique_lock<std::mutex> g;
+  DevEngine* cx = pick_context(eng, &g, heavy_search(*c, nq));
+  cx->inflight.fetch_add(1, std::memory_order_relaxed);
+  struct Leave {
+    DevEngine* cx;
+    ~Leave() { cx->inflight.fetch_sub(1, std::memory_order_relaxed); }
+  } leave{cx};
+  VS_HIP(set_dev(cx), "hipSetDevice");
+  VS_HIP(use_stream(cx, cx->own), "stream order");
+  const size_t qbytes = (size_t)nq * c->dim * 4;
+  const size_t kbytes = (size_t)nq * limit * group_size * 8;
+  const size_t gbytes = (size_t)nq * limit * 4;
+  if (cx->q_in.bytes < qbytes || cx->keys.bytes < kbytes || cx->grp_ids.bytes < gbytes) {
+    VS_HIP(hipStreamSynchronize(cx->stream), "sync");
+    VS_HIP(cx->q_in.ensure(qbytes), "alloc query input");
+    VS_HIP(cx->keys.ensure(kbytes), "alloc keys");
+    VS_HIP(cx->grp_ids.ensure(gbytes), "alloc group ids");
+  }
+  HostSlot* hs = nullptr;
+  for (auto& x : cx->host_slots)
+    if (!x->busy) {
+      hs = x.get();
+      break;
+    }
+  if (!hs) {
+    cx->host_slots.push_back(std::make_unique<HostSlot>());
+    hs = cx->host_slots.back().get();
+  }
+  VS_HIP(hs->ensure(qbytes, kbytes + gbytes), "alloc pinned staging");
+  std::memcpy(hs->in, queries, qbytes);
+  hs->busy = true;
+  auto abandon = [&](int rc) {
+    (void)hipStreamSynchronize(cx->stream);
+    hs->busy = false;
+    return rc;
+  };
+  hipError_t e = hipMemcpyAsync(cx->q_in.p, hs->in, qbytes, hipMemcpyHostToDevice, cx->stream);
+  if (e != hipSuccess) return abandon(fail_hip(e, "query H2D"));
+  const int rc = groups_core(cx, *c, cx->q_in.as<float>(), nq, limit, group_size, *dg, df.get(),
+                             cx->keys.as<uint64_t>(), cx->grp_ids.as<uint32_t>());
+  if (rc != VS_OK) return abandon(rc);
+  e = hipMemcpyAsync(hs->out, cx->keys.p, kbytes, hipMemcpyDeviceToHost, cx->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync((char*)hs->out + kbytes, cx->grp_ids.p, gbytes, hipMemcpyDeviceToHost,
+                       cx->stream);
+  if (e == hipSuccess) e = hipEventRecord(hs->done, cx->stream);
+  if (e != hipSuccess) return abandon(fail_hip(e, "keys D2H"));
+  g.unlock();  // wait outside work_mu, as search_host does
+  const hipError_t we = wait_event(hs->done);
+  if (we == hipSuccess)
+    decode_groups((const uint64_t*)hs->out, (const uint32_t*)((const char*)hs->out + kbytes), nq,
+                  limit, group_size, out_groups, out_hits, out_scores, out_rows, out_count);
+  g.lock();
+  hs->busy = false;
+  VS_HIP(we, "search sync");
+  return VS_OK;
+}
+
+int group_keys(DevEngine* eng, const char* coll, const float* d_queries, uint32_t nq,
+               uint32_t dim, uint32_t limit, uint32_t group_size, uint64_t grouping_id,
+               uint64_t filter_id, uint64_t* d_keys, uint32_t* d_groups, void* stream) {
+  if (!eng) return fail(VS_ERR_INVALID_ARG, "engine is NULL");
+  const int arc = groups_args(limit, group_size);
+  if (arc != VS_OK) return arc;
+  if (nq == 0) return VS_OK;
+  if (!d_queries || !d_keys || !d_groups) return fail(VS_ERR_INVALID_ARG, "NULL device pointer");
+  auto c = find_coll(eng, coll);
+  if (!c) return fail(VS_ERR_NOT_FOUND, std::string("collection ") + (coll ? coll : "") +
+                                            " not found");
+  if (dim != c->dim)
+    return fail(VS_ERR_DIM_MISMATCH, "Vector dimension error: expected dim: " +
+                                         std::to_string(c->dim) + ", got " + std::to_string(dim));
+  std::shared_lock<std::shared_mutex> rl(c->mu);
+  std::shared_ptr<DevGrouping> dg;
+  std::shared_ptr<DevFilter> df;
+  const int lrc = groups_lookup(eng, *c, grouping_id, filter_id, &dg, &df);
+  if (lrc != VS_OK) return lrc;
+  std::lock_guard<std::mutex> g(eng->work_mu);
+  VS_HIP(set_dev(eng), "hipSetDevice");
+  VS_HIP(use_stream(eng, (hipStream_t)stream), "stream order");
+  return groups_core(eng, *c, d_queries, nq, limit, group_size, *dg, df.get(), d_keys, d_groups);
 }
 
 int merge_keys(DevEngine* eng, const uint64_t* d_lists, uint32_t n_lists, uint32_t nq,

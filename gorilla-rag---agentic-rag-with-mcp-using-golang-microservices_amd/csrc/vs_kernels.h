@@ -487,6 +487,40 @@ hipError_t launch_mmr(const void* X, bool bf16, uint32_t dim, uint32_t n_rows, u
                       const uint64_t* cand, uint32_t nq, uint32_t n_cand, uint32_t k,
                       float diversity, uint64_t* out, hipStream_t st);
 
+// Grouped search (vs_group.hip; include/vsearch.h "Grouped search"), per query
+// after launch_gemv_scores. sc / gid: n_rows score images / group ids (an id
+// >= n_groups, VS_GROUP_NONE among them, is "no group" and never an index),
+// both 16-byte aligned; row_base + n_rows < 2^32. All on `st`, nothing but the
+// named outputs written.
+//  launch_group_best: best[g] (n_groups u64, zero on entry) = the largest key
+//    of group g's rows with a non-zero image; hist (nullable: the score pass's
+//    kRselBins counts) is cleared.
+//  launch_group_heads: lists[group_lists(n_rows)][limit] = every workgroup's
+//    largest head keys (rows whose key is their group's best), descending,
+//    0-padded: launch_merge(lists, L, limit, 0, 1, limit, limit, heads).
+//  launch_group_members: heads = [limit] keys, descending, 0-padded;
+//    lists[group_lists(n_rows)][limit][group_size] = per workgroup and returned
+//    group its largest member keys: launch_merge(lists, L, limit * group_size,
+//    group_size, limit, group_size, group_size, out) gives out[limit]
+//    [group_size]; groups[limit] = the heads' ids, kGroupNone past them.
+//  launch_group_clear: best[0, n_groups) = 0 again (one memset).
+constexpr uint32_t kGroupNone = 0xFFFFFFFFu;
+constexpr uint32_t kGroupsMaxLimit = 128;
+constexpr uint32_t kGroupsMaxSize = 16;
+constexpr uint32_t kGroupsMaxLists = 512;
+uint32_t group_lists(uint32_t n_rows);
+hipError_t launch_group_best(const uint32_t* sc, const uint32_t* gid, uint32_t n_rows,
+                             uint32_t row_base, uint32_t n_groups, uint64_t* best, uint32_t* hist,
+                             hipStream_t st);
+hipError_t launch_group_heads(const uint32_t* sc, const uint32_t* gid, const uint64_t* best,
+                              uint32_t n_rows, uint32_t row_base, uint32_t n_groups,
+                              uint32_t limit, uint64_t* lists, hipStream_t st);
+hipError_t launch_group_members(const uint32_t* sc, const uint32_t* gid, const uint64_t* best,
+                                uint32_t n_rows, uint32_t row_base, uint32_t n_groups,
+                                const uint64_t* heads, uint32_t limit, uint32_t group_size,
+                                uint64_t* lists, uint32_t* groups, hipStream_t st);
+hipError_t launch_group_clear(uint64_t* best, uint32_t n_groups, hipStream_t st);
+
 int device_cu_count();
 
 }  // namespace vsk

@@ -54,8 +54,12 @@ EXPORTS = (
     "vs_copy_last_error", "vs_build_id", "vs_collection_placement", "vs_runtime_check",
     "vs_collection_prefilter_bytes", "vs_collection_spec_stats", "vs_delete",
     "vs_search_mmr", "vs_mmr_keys",
+    "vs_grouping_create", "vs_grouping_drop", "vs_search_groups", "vs_group_keys",
 )
 MMR_MAX_CANDIDATES = 128
+GROUP_NONE = 0xFFFFFFFF
+GROUPS_MAX_LIMIT = 128
+GROUPS_MAX_SIZE = 16
 COMM_ID_BYTES = 128
 
 
@@ -160,6 +164,10 @@ def load_library(path: str = LIB_PATH):
         "vs_search_filter_id": ([vp, cp, vp, u32, u32, u32, u64, vp, vp, vp], i32),
         "vs_search_mmr": ([vp, cp, vp, u32, u32, u32, u32, ctypes.c_float, u64, vp, vp, vp], i32),
         "vs_mmr_keys": ([vp, cp, vp, u32, u32, u32, ctypes.c_float, vp, vp], i32),
+        "vs_grouping_create": ([vp, cp, vp, u64, u32, vp], i32),
+        "vs_grouping_drop": ([vp, u64], i32),
+        "vs_search_groups": ([vp, cp, vp, u32, u32, u32, u32, u64, u64, vp, vp, vp, vp, vp], i32),
+        "vs_group_keys": ([vp, cp, vp, u32, u32, u32, u32, u64, u64, vp, vp, vp], i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -450,6 +458,49 @@ class VectorEngine:
         _check(self._L.vs_mmr_keys(self._h, name.encode(), ctypes.c_void_p(d_cand_keys), nq,
                                    n_cand, k, diversity, ctypes.c_void_p(d_out_keys),
                                    ctypes.c_void_p(stream)))
+
+    def grouping_create(self, name: str, group_of_row: np.ndarray, n_groups: int) -> int:
+        """vs_grouping_create: one group id per row (< n_groups, or GROUP_NONE),
+        resident on the device; returns the id for search_groups."""
+        g = np.ascontiguousarray(group_of_row, np.uint32)
+        gid = ctypes.c_uint64()
+        _check(self._L.vs_grouping_create(self._h, name.encode(), _p(g), g.size, n_groups,
+                                          ctypes.byref(gid)))
+        return gid.value
+
+    def grouping_drop(self, grouping_id: int):
+        _check(self._L.vs_grouping_drop(self._h, grouping_id))
+
+    def search_groups(self, name: str, queries: np.ndarray, limit: int, group_size: int,
+                      grouping_id: int, filter_id: int = 0):
+        """vs_search_groups: the best `limit` groups of every query and the best
+        `group_size` rows of each. Returns (groups [nq, limit], hits [nq, limit],
+        scores [nq, limit, group_size], rows [nq, limit, group_size], count [nq]),
+        zero past the counts."""
+        q = np.ascontiguousarray(queries, np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        nq = q.shape[0]
+        shape = (nq, max(limit, 0), max(group_size, 0))
+        groups = np.zeros(shape[:2], np.uint32)
+        hits = np.zeros(shape[:2], np.uint32)
+        scores = np.zeros(shape, np.float32)
+        rows = np.zeros(shape, np.uint64)
+        count = np.zeros(nq, np.uint32)
+        _check(self._L.vs_search_groups(self._h, name.encode(), _p(q), nq, q.shape[1], limit,
+                                        group_size, grouping_id, filter_id, _p(groups), _p(hits),
+                                        _p(scores), _p(rows), _p(count)))
+        return groups, hits, scores, rows, count
+
+    def group_keys(self, name: str, d_queries: int, nq: int, dim: int, limit: int,
+                   group_size: int, grouping_id: int, filter_id: int, d_keys: int, d_groups: int,
+                   stream: int = 0):
+        """vs_group_keys: device queries -> [nq][limit][group_size] keys and
+        [nq][limit] group ids (GROUP_NONE past the count), on `stream`."""
+        _check(self._L.vs_group_keys(self._h, name.encode(), ctypes.c_void_p(d_queries), nq, dim,
+                                     limit, group_size, grouping_id, filter_id,
+                                     ctypes.c_void_p(d_keys), ctypes.c_void_p(d_groups),
+                                     ctypes.c_void_p(stream)))
 
     def search_keys(self, name: str, d_queries: int, nq: int, dim: int, k: int, d_keys: int,
                     stream: int = 0):

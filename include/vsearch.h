@@ -314,7 +314,7 @@ int vs_search_filter_id(vs_engine* eng, const char* coll, const float* queries, 
  * The stream and the pointers must come from the HIP runtime this library
  * is linked to: in a process that maps two libamdhip64 runtimes (e.g.
  * torch's bundled copy next to /opt/rocm's) this call and every other one
- * taking caller device pointers (vs_mmr_keys, vs_merge_keys, vs_gather_merge_keys,
+ * taking caller device pointers (vs_mmr_keys, vs_group_keys, vs_merge_keys, vs_gather_merge_keys,
  * vs_decode_keys, vs_generate_vectors) fail with VS_ERR_DEVICE rather than
  * run unordered with the caller's work. vs_runtime_check() runs that test
  * alone (no device needed): VS_OK, or VS_ERR_DEVICE naming both runtimes. */
@@ -383,6 +383,75 @@ int vs_search_mmr(vs_engine* eng, const char* coll, const float* queries, uint32
 int vs_mmr_keys(vs_engine* eng, const char* coll, const uint64_t* d_cand_keys, uint32_t nq,
                 uint32_t n_cand, uint32_t k, float diversity, uint64_t* d_out_keys,
                 void* stream);
+
+/* ---- Grouped search (the best groups and their best rows, on the device) ----
+ *
+ * Qdrant's SearchGroups (group_by, group_size, limit): the reference's ingest
+ * stores a document_id in every chunk's payload and its retrieval service
+ * regroups the hits by it (rag/retrieval-service/main.go:264-333). This
+ * returns the best `limit` groups of a query and the best `group_size` rows of
+ * each, exactly, without over-sampling and without the scores leaving the
+ * device.
+ *
+ * A GROUPING is a device-resident array of one group id per local row of a
+ * collection: group_of_row[r] < n_groups, or VS_GROUP_NONE (the row belongs to
+ * no group and never appears in a grouped answer).
+ *  - vs_grouping_create: n_rows must equal the collection's row count and
+ *    n_groups <= max(n_rows, 1); every id is checked on the host. Anything else
+ *    is VS_ERR_INVALID_ARG and nothing is created. Ids of groupings start at 1
+ *    and are never reused within an engine.
+ *  - A grouping is bound to the collection and its row count, as a filter is:
+ *    a grouped search after rows were appended fails with VS_ERR_INVALID_ARG;
+ *    vs_delete (of at least one row) and vs_collection_drop drop the
+ *    collection's groupings where they drop its filters, and a dropped or
+ *    unknown id is VS_ERR_NOT_FOUND. Ids are rows, not payloads: after an
+ *    overwrite that changes a row's document the caller rebuilds the grouping.
+ *
+ * For one query the ELIGIBLE rows are those with a group and, when filter_id
+ * != 0, allowed by that filter. Every row has the result key of "Result key
+ * layout" above; its score is exactly the bits vs_search returns for that
+ * query alone (nq = 1). Let B(g) be the largest key among group g's eligible
+ * rows. The answer is the min(limit, non-empty groups) groups with the largest
+ * B(g), in descending B(g): best score first, equal scores by the lower row
+ * (keys are distinct, so there are no ties). For each returned group it holds
+ * the group's min(group_size, eligible members) largest keys, descending.
+ *  - 1 <= limit <= VS_GROUPS_MAX_LIMIT, 1 <= group_size <= VS_GROUPS_MAX_SIZE,
+ *    else VS_ERR_INVALID_ARG.
+ *  - out_count[i] = groups returned for query i; out_groups / out_hits hold
+ *    their ids and their numbers of hits; out_scores / out_rows the hits.
+ *    All outputs keep their strides (limit, and limit x group_size) and are
+ *    zero past the counts. Any output pointer but out_count may be NULL.
+ *  - group_size = 1 with every row in its own group equals vs_search with
+ *    k = limit, key for key.
+ *  - Supported on vs_open engines and on placed collections
+ *    (VS_FLAG_PLACE_COLLECTIONS; the calls go to the home device). A
+ *    row-striped collection keeps its rows' groups on several devices:
+ *    vs_grouping_create and both searches return VS_ERR_INVALID_ARG there.
+ *    This limit is deliberate.
+ *  - A search: it takes the collection's reader lock for the whole call. A
+ *    batch (nq > 1) is answered query by query. */
+#define VS_GROUP_NONE       0xFFFFFFFFu /* the row belongs to no group */
+#define VS_GROUPS_MAX_LIMIT 128u        /* groups per query */
+#define VS_GROUPS_MAX_SIZE  16u         /* hits per group */
+int vs_grouping_create(vs_engine* eng, const char* coll, const uint32_t* group_of_row,
+                       uint64_t n_rows, uint32_t n_groups, uint64_t* grouping_id);
+int vs_grouping_drop(vs_engine* eng, uint64_t grouping_id);
+int vs_search_groups(vs_engine* eng, const char* coll, const float* queries, uint32_t nq,
+                     uint32_t dim, uint32_t limit, uint32_t group_size, uint64_t grouping_id,
+                     uint64_t filter_id /* 0 = none */,
+                     uint32_t* out_groups, /* [nq][limit] group ids, best group first */
+                     uint32_t* out_hits,   /* [nq][limit] hits returned for that group */
+                     float* out_scores,    /* [nq][limit][group_size] */
+                     uint64_t* out_rows,   /* [nq][limit][group_size] global rows */
+                     uint32_t* out_count); /* [nq] groups returned */
+/* Device-pointer form: d_queries is [nq][dim] fp32, d_keys [nq][limit]
+ * [group_size] receives the hits' result keys (0-padded past a group's hits and
+ * past the returned groups), d_groups [nq][limit] the group ids
+ * (VS_GROUP_NONE past the count). Ordered on `stream` as vs_search_keys is,
+ * under the same one-runtime rule (vs_runtime_check). */
+int vs_group_keys(vs_engine* eng, const char* coll, const float* d_queries, uint32_t nq,
+                  uint32_t dim, uint32_t limit, uint32_t group_size, uint64_t grouping_id,
+                  uint64_t filter_id, uint64_t* d_keys, uint32_t* d_groups, void* stream);
 
 /* Merges `n_lists` per-shard key lists into the global top-k on the device:
  * d_lists is [n_lists][nq][k_in] (e.g. the result of an all-gather of

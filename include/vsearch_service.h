@@ -51,6 +51,34 @@
  * with its relevance score. 501 when the engine library has no vs_search_mmr
  * (referenced weakly, as vs_delete).
  *
+ * /search also takes "group_by": "<payload key>" and "group_size": integer
+ * (Qdrant's SearchGroups; include/vsearch.h "Grouped search"). A null or
+ * absent "group_by" leaves the route exactly as it is (a "group_size" beside
+ * it is checked and unused). "group_size" defaults to 1, the best chunk per
+ * document. A "group_by" that is not a string, a "group_size" that is not an
+ * integer in [1, 16], or "group_by" together with "mmr" is 400 "Invalid
+ * request body". With it:
+ *  - top_k is the number of GROUPS; after the usual clamp to the collection's
+ *    rows it must be at most 128, else 400;
+ *  - the group of a point is the JSON value of payload[group_by] when that is
+ *    a string or an integer (Qdrant's keyword and integer group keys); a point
+ *    without the key, or with any other type there, has no group and never
+ *    appears. Dense group ids are given in first-seen row order;
+ *  - the grouping is made resident once (vs_grouping_create) and cached per
+ *    (collection, key) beside the filter masks; the next /upsert or /delete of
+ *    the collection invalidates it and the next grouped search rebuilds it
+ *    (500 with the engine's message if it cannot be made resident). A
+ *    collection holding bulk-generated points has no payloads: 400;
+ *  - the request goes straight to vs_search_groups with one query (not
+ *    through the batcher), under the resident filter when "filter":"match" is
+ *    configured and a filter is given;
+ *  - the reply's "results" is flat, in group order with a group's hits
+ *    adjacent (the retrieval service's decoder reads it unchanged), "count"
+ *    is its length, and "groups": [{"id": <the payload value>, "hits": n}, ...]
+ *    follows in the same order.
+ * 501 when the engine library lacks vs_search_groups, vs_grouping_create or
+ * vs_grouping_drop (referenced weakly).
+ *
  * Point UUIDs and payloads live here (a UUID -> row map and a row-indexed
  * payload store per collection); the engine sees dense rows only. A Go
  * deployment binds the same engine C-ABI through cgo and
