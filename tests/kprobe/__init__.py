@@ -22,11 +22,20 @@ _CONSTS64 = ["q8_glob_bytes", "q8_spec_stat_off", "q8_spec_k_off", "q8_spec_k_si
              "spec_stat_skipped_off", "q8_par_bytes", "rsel_state_size", "rsel_state_thr_off",
              "rsel_state_krem_off", "rsel_state_done_off", "rsel_state_count_off"]
 _CONSTS32 = ["gate_verdict", "gate_forced", "gate_go", "q8_spec_probe", "q8_spec_max_backoff",
-             "mfma_query_slots", "mfma_max_k", "mfma_max_cand_cap", "rsel_bins", "max_k"]
+             "mfma_query_slots", "mfma_max_k", "mfma_max_cand_cap", "rsel_bins", "max_k",
+             "gemv_small_arg_dim", "gemv_small_max_rows", "gemv_small_max_k", "gemv_small_max_parts"]
 _SIGS = {
     "device_cu_count": (u32, []),
     "gemv_scores": (i32, [u64, i32, u32, u32, u64, u64, u64, u64]),
     "gemv": (i32, [u64, i32, u32, u32, u32, u64, u32, u64, u32, pu32, u64]),
+    "gemv_gather": (i32, [u64, i32, u32, u32, u32, u64, u32, u64, u32, pu32, u64]),
+    "compact_scratch_words": (u32, [u32]),
+    "compact_rows": (i32, [u64, u32, u64, u64]),
+    "gemv_small_ok": (i32, [u32, u32, u32]),
+    "gemv_small_parts": (u32, [u32, i32, u32]),
+    "gemv_one_ok": (i32, [u32, u32]),
+    "gemv_small": (i32, [u64, i32, u32, u32, u32, u64, i32, u32, u64, u64, u64, u64]),
+    "gemv_one_host": (i32, [u64, i32, u32, u32, u32, u64, i32, u64, u32, u64, u32, pu32]),
     "rsel": (i32, [u64, u32, u32, u32, u64, u64, u64]),
     "rsel_fused": (i32, [u64, u32, u32, u32, u64, u64, u64, u64, u64]),
     "sort_keys_temp_bytes": (u64, [u64]),

@@ -6,9 +6,12 @@
 // test_q8_gemv_stages_gpu.py are the users), and each piece of the large-k
 // path (test_rsel_stages_gpu.py: both selections on score images the test
 // builds; test_large_k_stages_gpu.py: the score pass, the key sort, the sort
-// merge and the key remap). The sort merge's walk used to end at the first
-// 256-key chunk that kept nothing, which a key repeated in more than 256 lists
-// produces with distinct keys still behind it; it now ends at the zero padding.
+// merge and the key remap), and the plain one-query scan
+// (test_gemv_stages_gpu.py: launch_gemv with and without a row list,
+// launch_gemv_one, launch_gemv_small, launch_compact_rows). The sort merge's
+// walk used to end at the first 256-key chunk that kept nothing, which a key
+// repeated in more than 256 lists produces with distinct keys still behind it;
+// it now ends at the zero padding.
 //
 // Host C++ only: no kernels and no HIP runtime call. Every pointer is a raw
 // device address (uint64_t, a torch tensor's data_ptr()), every launch goes to
@@ -256,6 +259,49 @@ int kp_gemv(uint64_t X, int bf16, uint32_t dim, uint32_t n_rows, uint32_t row_ba
   return (int)vsk::launch_gemv(P<const void>(X), bf16 != 0, dim, n_rows, row_base, P<const float>(q),
                                k, P<uint64_t>(out), max_lists, nlists, kSt,
                                P<const uint64_t>(allow), nullptr);
+}
+// ---- the plain one-query family (test_gemv_stages_gpu.py) -----------------------
+uint32_t kp_gemv_small_arg_dim() { return vsk::kGemvSmallArgDim; }
+uint32_t kp_gemv_small_max_rows() { return vsk::kGemvSmallMaxRows; }
+uint32_t kp_gemv_small_max_k() { return vsk::kGemvSmallMaxK; }
+uint32_t kp_gemv_small_max_parts() { return vsk::kGemvSmallMaxParts; }
+// rows: n_rows local row indices on the device; the scan gathers them
+int kp_gemv_gather(uint64_t X, int bf16, uint32_t dim, uint32_t n_rows, uint32_t row_base,
+                   uint64_t q, uint32_t k, uint64_t out, uint32_t max_lists, uint32_t* nlists,
+                   uint64_t rows) {
+  return (int)vsk::launch_gemv(P<const void>(X), bf16 != 0, dim, n_rows, row_base, P<const float>(q),
+                               k, P<uint64_t>(out), max_lists, nlists, kSt, nullptr,
+                               P<const uint32_t>(rows));
+}
+uint32_t kp_compact_scratch_words(uint32_t n_rows) { return vsk::compact_scratch_words(n_rows); }
+int kp_compact_rows(uint64_t allow, uint32_t n_rows, uint64_t rows, uint64_t scratch) {
+  return (int)vsk::launch_compact_rows(P<const uint64_t>(allow), n_rows, P<uint32_t>(rows),
+                                       P<uint32_t>(scratch), kSt);
+}
+int kp_gemv_small_ok(uint32_t dim, uint32_t n_rows, uint32_t k) {
+  return vsk::gemv_small_ok(dim, n_rows, k) ? 1 : 0;
+}
+uint32_t kp_gemv_small_parts(uint32_t dim, int bf16, uint32_t n_rows) {
+  return vsk::gemv_small_parts(dim, bf16 != 0, n_rows);
+}
+int kp_gemv_one_ok(uint32_t dim, uint32_t k) { return vsk::gemv_one_ok(dim, k) ? 1 : 0; }
+// part / counter: 0 = one workgroup; q_host: a HOST address (0 = read q_raw on
+// the device); no completion word
+int kp_gemv_small(uint64_t X, int bf16, uint32_t dim, uint32_t n_rows, uint32_t row_base,
+                  uint64_t q_raw, int cosine, uint32_t k, uint64_t out, uint64_t part,
+                  uint64_t counter, uint64_t q_host) {
+  return (int)vsk::launch_gemv_small(P<const void>(X), bf16 != 0, dim, n_rows, row_base,
+                                     P<const float>(q_raw), cosine != 0, k, P<uint64_t>(out), kSt,
+                                     P<uint64_t>(part), P<uint32_t>(counter), nullptr, 0,
+                                     P<const float>(q_host));
+}
+// kp_gemv_one with the raw query at a HOST address (it travels in the kernel arguments)
+int kp_gemv_one_host(uint64_t X, int bf16, uint32_t dim, uint32_t n_rows, uint32_t row_base,
+                     uint64_t q_host, int cosine, uint64_t allow, uint32_t k, uint64_t lists,
+                     uint32_t max_lists, uint32_t* nlists) {
+  return (int)vsk::launch_gemv_one(P<const void>(X), bf16 != 0, dim, n_rows, row_base, nullptr,
+                                   cosine != 0, P<const uint64_t>(allow), k, P<uint64_t>(lists),
+                                   max_lists, kSt, nlists, P<const float>(q_host));
 }
 int kp_rsel(uint64_t sc, uint32_t n_rows, uint32_t row_base, uint32_t keff, uint64_t hist,
             uint64_t state, uint64_t sel) {

@@ -119,7 +119,7 @@ def _list_path_keys(kp, torch, Xd, bf16, dim, n, qd, allow_ptr):
 
 
 @pytest.mark.parametrize("bf16", [0, 1])
-@pytest.mark.parametrize("dim", [768, 1024, 1536, 100])
+@pytest.mark.parametrize("dim", [768, 1024, 1536, 100, 2048, 3072, 4096])
 def test_gemv_scores(kp, torch_, corpora, dim, bf16):
     Xd, qd, s64 = corpora(dim, bf16)
     rng = np.random.default_rng(dim + bf16)
