@@ -326,6 +326,19 @@ type searchBody struct {
 	// an extension: Qdrant's SearchGroups (include/vsearch_service.h)
 	GroupBy   *string `json:"group_by"`
 	GroupSize *int    `json:"group_size"` // default 1: the best chunk per document
+	Fusion    *fusionBody `json:"fusion"` // an extension: Qdrant's query-API prefetch + fusion
+}
+
+// fusionBody is /search's optional "fusion" object (include/vsearch_service.h):
+// the request's own query is sub-query 0 and Queries holds 1 to 7 more vectors
+// (decoded loosely: toFloat32 applies convertVector's rules to each); Method
+// defaults to "rrf", PrefetchLimit to 0 (the engine's min(4 top_k, 128)) and
+// RRFK to 0 (the engine's 2; not allowed with "dbsf").
+type fusionBody struct {
+	Method        *string       `json:"method"`
+	Queries       []interface{} `json:"queries"`
+	PrefetchLimit *int          `json:"prefetch_limit"`
+	RRFK          *int          `json:"rrf_k"`
 }
 
 // mmrBody is /search's optional "mmr" object (include/vsearch_service.h): both
@@ -462,6 +475,42 @@ func (s *service) search(w http.ResponseWriter, r *http.Request) {
 		writeError(w, http.StatusBadRequest, "Invalid request body")
 		return
 	}
+	fusion, prefetch, rrfK := vsearch.FusionRRF, uint32(0), uint32(0)
+	var subs [][]float32 // fusion.queries, converted
+	if f := body.Fusion; f != nil {
+		if f.Method != nil {
+			switch *f.Method {
+			case "rrf":
+			case "dbsf":
+				fusion = vsearch.FusionDBSF
+			default:
+				writeError(w, http.StatusBadRequest, "Invalid request body")
+				return
+			}
+		}
+		bad := len(f.Queries) == 0 || len(f.Queries) > int(vsearch.FuseMaxLists)-1 ||
+			(f.PrefetchLimit != nil && (*f.PrefetchLimit < 0 || *f.PrefetchLimit > int(vsearch.FuseMaxLimit))) ||
+			(f.RRFK != nil && (*f.RRFK < 0 || *f.RRFK > 65536 || fusion == vsearch.FusionDBSF)) ||
+			body.MMR != nil || body.GroupBy != nil
+		if bad {
+			writeError(w, http.StatusBadRequest, "Invalid request body")
+			return
+		}
+		if f.PrefetchLimit != nil {
+			prefetch = uint32(*f.PrefetchLimit)
+		}
+		if f.RRFK != nil {
+			rrfK = uint32(*f.RRFK)
+		}
+		for _, q := range f.Queries {
+			v, err := toFloat32(q)
+			if err != nil {
+				writeError(w, http.StatusBadRequest, err.Error())
+				return
+			}
+			subs = append(subs, v)
+		}
+	}
 	log.Printf("Searching in collection: %s, TopK: %d", body.Collection, body.TopK)
 	st := s.store(body.Collection)
 	if st == nil {
@@ -476,6 +525,13 @@ func (s *service) search(w http.ResponseWriter, r *http.Request) {
 			"Search failed: Vector dimension error: expected dim: %d, got %d", s.dim, len(body.Query)))
 		return
 	}
+	for _, v := range subs {
+		if uint32(len(v)) != s.dim {
+			writeError(w, http.StatusInternalServerError, fmt.Sprintf(
+				"Search failed: Vector dimension error: expected dim: %d, got %d", s.dim, len(v)))
+			return
+		}
+	}
 	if body.GroupBy != nil {
 		s.searchGroups(w, &body, st, groupSize)
 		return
@@ -487,7 +543,28 @@ func (s *service) search(w http.ResponseWriter, r *http.Request) {
 			k = rows
 		}
 		hits, err := vsearch.Hits{}, error(nil)
-		if body.MMR != nil {
+		if body.Fusion != nil {
+			// one engine call per request, past the batcher: query and fusion.queries
+			// are the sub-queries of one fused query; scores are the fused scores
+			if k > int(vsearch.FuseMaxLimit) {
+				writeError(w, http.StatusBadRequest, fmt.Sprintf(
+					"top_k must not exceed %d with fusion", vsearch.FuseMaxLimit))
+				return
+			}
+			if prefetch != 0 && prefetch < uint32(k) {
+				prefetch = uint32(k)
+			}
+			all := append([]float32{}, body.Query...)
+			for _, v := range subs {
+				all = append(all, v...)
+			}
+			var hs []vsearch.Hits
+			hs, err = s.eng.SearchFused(body.Collection, all, uint32(1+len(subs)), s.dim, uint32(k),
+				prefetch, fusion, rrfK, 0)
+			if err == nil {
+				hits = hs[0]
+			}
+		} else if body.MMR != nil {
 			// one engine call per request, past the batcher; results in selection order
 			if k > int(vsearch.MMRMaxCandidates) {
 				writeError(w, http.StatusBadRequest, fmt.Sprintf(

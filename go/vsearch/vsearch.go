@@ -103,6 +103,15 @@ static int vsg_group_keys(vs_engine* h, const char* n, const float* q, uint32_t 
                           uint32_t* g, void* st, vsg_err* e) {
 	return vsg_fin(vs_group_keys(h, n, q, nq, d, limit, size, gid, fid, k, g, st), e);
 }
+static int vsg_search_fused(vs_engine* h, const char* n, const float* q, uint32_t nq, uint32_t ns,
+                            uint32_t d, uint32_t k, uint32_t pf, int fusion, uint32_t rk,
+                            uint64_t fid, float* s, uint64_t* r, uint32_t* c, vsg_err* e) {
+	return vsg_fin(vs_search_fused(h, n, q, nq, ns, d, k, pf, fusion, rk, fid, s, r, c), e);
+}
+static int vsg_fuse_keys(vs_engine* h, const uint64_t* l, uint32_t nq, uint32_t ns, uint32_t kin,
+                         uint32_t k, int fusion, uint32_t rk, uint64_t* o, void* st, vsg_err* e) {
+	return vsg_fin(vs_fuse_keys(h, l, nq, ns, kin, k, fusion, rk, o, st), e);
+}
 static int vsg_filter_create(vs_engine* h, const char* n, const uint64_t* a, uint64_t aw,
                              uint64_t* id, vsg_err* e) {
 	return vsg_fin(vs_filter_create(h, n, a, aw, id), e);
@@ -629,6 +638,67 @@ func (e *Engine) GroupKeys(name string, dQueries unsafe.Pointer, nq, dim, limit,
 	return check(C.vsg_group_keys(e.h, cs, (*C.float)(dQueries), C.uint32_t(nq), C.uint32_t(dim),
 		C.uint32_t(limit), C.uint32_t(groupSize), C.uint64_t(groupingID), C.uint64_t(filterID),
 		(*C.uint64_t)(dKeys), (*C.uint32_t)(dGroups), stream, &ce), &ce)
+}
+
+// Fusion methods (vs_fusion) and the limits of a fused search.
+const (
+	FusionRRF  = int(C.VS_FUSION_RRF)
+	FusionDBSF = int(C.VS_FUSION_DBSF)
+	// FuseMaxLists is VS_FUSE_MAX_LISTS: the most sub-queries of one fused query.
+	FuseMaxLists = uint32(C.VS_FUSE_MAX_LISTS)
+	// FuseMaxLimit is VS_FUSE_MAX_LIMIT: the largest prefetch_limit (and k).
+	FuseMaxLimit = uint32(C.VS_FUSE_MAX_LIMIT)
+)
+
+// SearchFused searches the nSub sub-queries of every fused query as one batch
+// for prefetchLimit rows each (0 = min(4k, 128)) and fuses their ranked lists
+// on the device (vs_search_fused): queries holds [nq][nSub][dim] floats, and
+// Hits carry the FUSED score. fusion is FusionRRF (rrfK = Qdrant's constant,
+// 0 = 2) or FusionDBSF (rrfK must be 0); filterID (0 = none) is a filter made
+// by FilterCreate. The reference searches with one of its planner's
+// rewritten_queries (agent/orchestrator-service/main.go:531-568); this takes
+// all of them.
+func (e *Engine) SearchFused(name string, queries []float32, nSub, dim, k, prefetchLimit uint32,
+	fusion int, rrfK uint32, filterID uint64) ([]Hits, error) {
+	if dim == 0 || nSub == 0 || len(queries) == 0 || len(queries)%int(dim*nSub) != 0 {
+		return nil, fmt.Errorf("vsearch: %d floats are not whole fused queries of %d x dim %d: %w",
+			len(queries), nSub, dim, ErrInvalidArg)
+	}
+	if k == 0 {
+		return nil, fmt.Errorf("vsearch: k must be at least 1: %w", ErrInvalidArg)
+	}
+	nq := len(queries) / int(dim*nSub)
+	cs := C.CString(name)
+	defer C.free(unsafe.Pointer(cs))
+	rows := make([]uint64, nq*int(k))
+	scores := make([]float32, nq*int(k))
+	count := make([]uint32, nq)
+	var ce C.vsg_err
+	rc := C.vsg_search_fused(e.h, cs, (*C.float)(unsafe.Pointer(&queries[0])), C.uint32_t(nq),
+		C.uint32_t(nSub), C.uint32_t(dim), C.uint32_t(k), C.uint32_t(prefetchLimit), C.int(fusion),
+		C.uint32_t(rrfK), C.uint64_t(filterID), (*C.float)(unsafe.Pointer(&scores[0])),
+		(*C.uint64_t)(unsafe.Pointer(&rows[0])), (*C.uint32_t)(unsafe.Pointer(&count[0])), &ce)
+	if err := check(rc, &ce); err != nil {
+		return nil, err
+	}
+	out := make([]Hits, nq)
+	for i := range out {
+		lo, n := i*int(k), int(count[i])
+		out[i] = Hits{Rows: rows[lo : lo+n], Scores: scores[lo : lo+n]}
+	}
+	return out, nil
+}
+
+// FuseKeys is the fusion stage alone (vs_fuse_keys): dLists holds
+// [nq][nSub][kIn] device keys as vs_search_keys writes them, dOut receives
+// [nq][k] keys carrying the fused score, descending, both on `stream` (a
+// hipStream_t; nil = the null stream). No collection is involved.
+func (e *Engine) FuseKeys(dLists, dOut unsafe.Pointer, nq, nSub, kIn, k uint32, fusion int,
+	rrfK uint32, stream unsafe.Pointer) error {
+	var ce C.vsg_err
+	return check(C.vsg_fuse_keys(e.h, (*C.uint64_t)(dLists), C.uint32_t(nq), C.uint32_t(nSub),
+		C.uint32_t(kIn), C.uint32_t(k), C.int(fusion), C.uint32_t(rrfK), (*C.uint64_t)(dOut),
+		stream, &ce), &ce)
 }
 
 // Snapshot writes a collection's stored rows to path (replaces Qdrant's

@@ -48,6 +48,7 @@ SOURCES = {
     "vs_delete.o": (["vs_delete.hip"], ["--offload-arch=" + ARCH, "-O3"]),
     "vs_mmr.o": (["vs_mmr.hip"], ["--offload-arch=" + ARCH, "-O3"]),
     "vs_group.o": (["vs_group.hip"], ["--offload-arch=" + ARCH, "-O3"]),
+    "vs_fuse.o": (["vs_fuse.hip"], ["--offload-arch=" + ARCH, "-O3"]),
     "vs_engine.o": (["vs_engine.cpp"], ["-O2", "-Wall"]),
     "vs_api.o": (["vs_api.cpp"], ["-O2", "-Wall"]),
 }

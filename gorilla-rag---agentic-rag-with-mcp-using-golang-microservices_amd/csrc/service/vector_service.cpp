@@ -45,6 +45,11 @@ extern "C" int vs_search_groups(vs_engine* eng, const char* coll, const float* q
                                 uint64_t grouping_id, uint64_t filter_id, uint32_t* out_groups,
                                 uint32_t* out_hits, float* out_scores, uint64_t* out_rows,
                                 uint32_t* out_count) __attribute__((weak));
+// ... and the fused search: without it a /search carrying "fusion" answers 501.
+extern "C" int vs_search_fused(vs_engine* eng, const char* coll, const float* queries, uint32_t nq,
+                               uint32_t n_sub, uint32_t dim, uint32_t k, uint32_t prefetch_limit,
+                               int fusion, uint32_t rrf_k, uint64_t filter_id, float* out_scores,
+                               uint64_t* out_rows, uint32_t* out_count) __attribute__((weak));
 
 namespace {
 
@@ -249,6 +254,16 @@ struct SearchRequest {  // main.go:26-31
   bool has_group = false;
   std::string group_by;
   uint32_t group_size = 1;  // the best chunk per document
+  // "fusion": {"method": "rrf"|"dbsf", "queries": [[...], ...], "prefetch_limit":
+  // integer, "rrf_k": integer} (an extension: Qdrant's query-API prefetch +
+  // fusion; include/vsearch.h "Fused search"). `query` is sub-query 0 and
+  // fusion.queries holds 1 to 7 more, kept as decoded until convertVector's
+  // rules are applied to them
+  bool has_fusion = false;
+  int fusion_method = VS_FUSION_RRF;
+  std::vector<Json> fusion_queries;
+  uint32_t fusion_prefetch = 0;  // 0: the engine's default, min(4 k, 128)
+  uint32_t fusion_rrf_k = 0;     // 0: the engine's default, 2
 };
 
 // A JSON number literal at b[i..) (the grammar json.Decoder accepts):
@@ -493,6 +508,60 @@ std::string decode_search_generic(const char* body, size_t len, SearchRequest* r
     }
   }
   if (req->has_group && req->has_mmr && first.empty()) first = "group_by: not allowed with mmr";
+  // "fusion" (null: absent): "queries" is required, 1 to VS_FUSE_MAX_LISTS - 1
+  // elements of any type (convertVector judges them later); "method" defaults
+  // to "rrf"; a null field keeps its default. A wrong type, an unknown method,
+  // a prefetch_limit outside [0, VS_FUSE_MAX_LIMIT], an rrf_k outside
+  // [0, 65536] or given with "dbsf", and fusion together with mmr or group_by
+  // are decode errors
+  if (const Json* fu = root.field("fusion")) {
+    if (fu->kind == Json::Object) {
+      req->has_fusion = true;
+      if (const Json* m = fu->field("method")) {
+        if (m->kind == Json::String && m->str == "rrf") req->fusion_method = VS_FUSION_RRF;
+        else if (m->kind == Json::String && m->str == "dbsf") req->fusion_method = VS_FUSION_DBSF;
+        else if (m->kind != Json::Null && first.empty()) first = "fusion.method: not rrf or dbsf";
+      }
+      const Json* qs = fu->field("queries");
+      if (qs && qs->kind == Json::Array && !qs->arr.empty() &&
+          qs->arr.size() <= VS_FUSE_MAX_LISTS - 1) {
+        if (!interface_numbers_ok(*qs) && first.empty()) first = "fusion.queries: number out of range";
+        req->fusion_queries = qs->arr;
+      } else if (first.empty()) {
+        first = "fusion.queries: not an array of 1 to 7 vectors";
+      }
+      if (const Json* p = fu->field("prefetch_limit")) {
+        int64_t v;
+        if (p->kind == Json::Number) {
+          if (!vsjson::parse_int64(p->str, &v) || v < 0 || v > (int64_t)VS_FUSE_MAX_LIMIT) {
+            if (first.empty()) first = "fusion.prefetch_limit: not an integer in [0, 128]";
+          } else {
+            req->fusion_prefetch = (uint32_t)v;
+          }
+        } else if (p->kind != Json::Null && first.empty()) {
+          first = "fusion.prefetch_limit: not a number";
+        }
+      }
+      if (const Json* r = fu->field("rrf_k")) {
+        int64_t v;
+        if (r->kind == Json::Number) {
+          if (!vsjson::parse_int64(r->str, &v) || v < 0 || v > 65536) {
+            if (first.empty()) first = "fusion.rrf_k: not an integer in [0, 65536]";
+          } else if (req->fusion_method == VS_FUSION_DBSF) {
+            if (first.empty()) first = "fusion.rrf_k: not allowed with dbsf";
+          } else {
+            req->fusion_rrf_k = (uint32_t)v;
+          }
+        } else if (r->kind != Json::Null && first.empty()) {
+          first = "fusion.rrf_k: not a number";
+        }
+      }
+    } else if (fu->kind != Json::Null && first.empty()) {
+      first = "fusion: not an object";
+    }
+  }
+  if (req->has_fusion && (req->has_mmr || req->has_group) && first.empty())
+    first = "fusion: not allowed with mmr or group_by";
   return first;
 }
 
@@ -954,12 +1023,23 @@ Response handle_search(vsvc* svc, const std::string& method, const char* body, s
     return error_json("MMR search is not supported by this engine", 501);
   if (req.has_group && !(vs_search_groups && vs_grouping_create && vs_grouping_drop))
     return error_json("Grouped search is not supported by this engine", 501);
+  // the extra sub-queries of a fused request: convertVector's rules and texts
+  std::vector<std::vector<float>> extra(req.fusion_queries.size());
+  for (size_t i = 0; i < extra.size(); ++i) {
+    std::string verr;
+    if (!convert_vector(req.fusion_queries[i], &extra[i], &verr)) return error_json(verr, 400);
+  }
+  if (req.has_fusion && !vs_search_fused)
+    return error_json("Fused search is not supported by this engine", 501);
 
   auto cs = svc->find(req.collection);
   if (!cs) return error_json("Search failed: " + not_found(req.collection), 500);
   std::shared_lock<std::shared_mutex> rl(cs->mu);
   if (req.query.size() != cs->dim)
     return error_json("Search failed: " + dim_error(cs->dim, req.query.size()), 500);
+  for (const auto& v : extra)
+    if (v.size() != cs->dim)
+      return error_json("Search failed: " + dim_error(cs->dim, v.size()), 500);
   const uint64_t rows = cs->nrows();
   // Qdrant returns min(limit, points): any limit is served (k > 1024 takes
   // the engine's large-k select), and buffers are sized by what can return
@@ -973,7 +1053,34 @@ Response handle_search(vsvc* svc, const std::string& method, const char* body, s
   // reply is encoded, so rows and UUIDs cannot change underneath.
   int rc;
   std::string err;
-  if (req.has_mmr) {
+  if (req.has_fusion) {
+    // Fused search (an extension; include/vsearch.h "Fused search"): `query` and
+    // fusion.queries go to the engine as the sub-queries of ONE fused query, in
+    // one call past the batcher. The reply has the same shape; its scores are
+    // the fused scores.
+    if (k > VS_FUSE_MAX_LIMIT)
+      return error_json("top_k must not exceed " + std::to_string(VS_FUSE_MAX_LIMIT) +
+                            " with fusion",
+                        400);
+    uint32_t prefetch = req.fusion_prefetch;  // 0 stays the engine's default (>= k)
+    if (prefetch != 0 && prefetch < k) prefetch = (uint32_t)k;
+    uint64_t fid = 0;
+    if (svc->filter_match && req.filter.kind == Json::Object && !req.filter.obj.empty()) {
+      fid = filter_mask(svc->eng, req.collection, *cs, req.filter).device_id;
+      if (!fid) {  // vs_search_fused takes a resident filter only
+        err = last_error();
+        if (err.empty()) err = "the filter could not be made resident";
+        return error_json("Search failed: " + grpc_error(VS_ERR_INTERNAL, err), 500);
+      }
+    }
+    std::vector<float> subs(req.query);
+    for (const auto& v : extra) subs.insert(subs.end(), v.begin(), v.end());
+    rc = vs_search_fused(svc->eng, req.collection.c_str(), subs.data(), 1,
+                         (uint32_t)(1 + extra.size()), cs->dim, (uint32_t)k, prefetch,
+                         req.fusion_method, req.fusion_rrf_k, fid, scores.data(), hit_rows.data(),
+                         &count);
+    if (rc != VS_OK) err = last_error();
+  } else if (req.has_mmr) {
     // MMR (an extension; include/vsearch.h "MMR search"): one engine call per
     // request, past the batcher (its batches are plain searches). Results come
     // back in selection order, in the same reply shape.

@@ -576,6 +576,91 @@ int groups_striped() {
               "live on several devices); use a vs_open engine or VS_FLAG_PLACE_COLLECTIONS");
 }
 
+// vs_search_fused of a row-striped collection (arguments as vsd::fuse_args left
+// them): sharded_search_host's striped half with the fusion stage on dev 0
+// between the global candidate search and the D2H. Fusion reads keys only, and
+// the merged lists on dev 0 are the global ones, so no layout is refused.
+int striped_search_fused_host(vs_engine* E, SColl& sc, const float* queries, uint32_t nq,
+                              uint32_t n_sub, uint32_t dim, uint32_t k, uint32_t limit, int fusion,
+                              uint32_t rrf_k, const SFilter* f, uint64_t filter_id,
+                              float* out_scores, uint64_t* out_rows, uint32_t* out_count) {
+  if (dim != sc.dim)
+    return fail(VS_ERR_DIM_MISMATCH, "Vector dimension error: expected dim: " +
+                                         std::to_string(sc.dim) + ", got " + std::to_string(dim));
+  std::shared_lock<std::shared_mutex> rl(sc.mu);
+  if (f && (f->coll_gen != sc.gen || f->rows != sc.rows))
+    return fail(VS_ERR_INVALID_ARG, "filter " + std::to_string(filter_id) +
+                                        " was built for another collection state");
+  // lists of min(limit, rows) keys, min(k, that) fused keys; the outputs keep stride k
+  const uint32_t ko = k, nsq = nq * n_sub;
+  const uint32_t F = (uint32_t)std::min<uint64_t>(limit, std::max<uint64_t>(sc.rows, 1));
+  k = std::min(k, F);
+  const size_t qbytes = (size_t)nsq * dim * 4, kbytes = (size_t)nq * k * 8;
+  std::vector<std::vector<uint64_t>> bits_keep;
+  std::vector<std::shared_ptr<vsd::DevFilter>> fkeep;  // alive until the wait below
+  vsd::Collection probe;
+  probe.dim = sc.dim;
+  probe.dtype = sc.dtype;
+  probe.rows = sc.rows / std::max<uint32_t>(1, E->shards());
+  AllWork aw;
+  CtxSet& cx = *pick_set(E, &aw, vsd::heavy_search(probe, nsq));
+  cx.inflight.fetch_add(1, std::memory_order_relaxed);
+  struct Leave {
+    CtxSet& cx;
+    ~Leave() { cx.inflight.fetch_sub(1, std::memory_order_relaxed); }
+  } leave{cx};
+  DevEngine* d0 = cx.dev[0];
+  vsd::HostSlot* hs = nullptr;
+  for (auto& x : cx.host_slots)
+    if (!x->busy) {
+      hs = x.get();
+      break;
+    }
+  if (!hs) {
+    cx.host_slots.push_back(std::make_unique<vsd::HostSlot>());
+    hs = cx.host_slots.back().get();
+  }
+  VS_HIP(vsd::set_dev(d0), "hipSetDevice");
+  if (d0->keys.bytes < kbytes) {  // the fused keys: dev 0's own result buffer
+    VS_HIP(hipStreamSynchronize(d0->stream), "sync");
+    VS_HIP(d0->keys.ensure(kbytes), "alloc keys");
+  }
+  VS_HIP(hs->ensure(qbytes, kbytes), "alloc pinned staging");
+  std::memcpy(hs->in, queries, qbytes);
+  hs->busy = true;
+  auto abandon = [&](int rc) {
+    const std::string msg = vsd::last_error();
+    for (DevEngine* de : cx.dev) {
+      (void)vsd::set_dev(de);
+      (void)hipStreamSynchronize(de->stream);
+    }
+    hs->busy = false;
+    return fail(rc, msg);
+  };
+  // the global lists land in the set's result buffer on dev 0, [nsq][F]
+  int rc = sharded_search(E, cx, sc, (const float*)hs->in, nullptr, false, nullptr, nsq, F, nullptr,
+                          &bits_keep, f, &fkeep, nullptr);
+  if (rc != VS_OK) return abandon(rc);
+  hipError_t e = vsd::set_dev(d0);
+  if (e != hipSuccess) return abandon(vsd::fail_hip(e, "hipSetDevice"));
+  rc = vsd::fuse_core(d0, cx.scr[0].out.as<uint64_t>(), nq, n_sub, F, k, fusion, rrf_k,
+                      d0->keys.as<uint64_t>());
+  if (rc != VS_OK) return abandon(rc);
+  e = hipMemcpyAsync(hs->out, d0->keys.p, kbytes, hipMemcpyDeviceToHost, d0->stream);
+  if (e == hipSuccess) e = hipEventRecord(hs->done, d0->stream);
+  if (e != hipSuccess) return abandon(vsd::fail_hip(e, "keys D2H"));
+  aw.locks.clear();  // wait outside the work locks, as sharded_search_host does
+  const hipError_t we = vsd::wait_event(hs->done);
+  if (we == hipSuccess)
+    vsd::decode_host((const uint64_t*)hs->out, nq, k, out_scores, out_rows, out_count, ko);
+  {
+    std::lock_guard<std::mutex> g(d0->work_mu);
+    hs->busy = false;
+  }
+  VS_HIP(we, "search sync");
+  return VS_OK;
+}
+
 // The home device's ids of a placed collection's grouping and filter (0: none).
 int placed_group_ids(vs_engine* E, const SColl& sc, uint64_t grouping_id, uint64_t filter_id,
                      uint64_t* dev_gid, uint64_t* dev_fid) {
@@ -1570,6 +1655,51 @@ int vs_mmr_keys(vs_engine* eng, const char* coll, const uint64_t* d_cand_keys, u
                          d_out_keys, stream);
   return placed_mmr_keys(eng, *sc, d_cand_keys, nq, n_cand, k, diversity, d_out_keys,
                          (hipStream_t)stream);
+}
+
+int vs_search_fused(vs_engine* eng, const char* coll, const float* queries, uint32_t nq,
+                    uint32_t n_sub, uint32_t dim, uint32_t k, uint32_t prefetch_limit, int fusion,
+                    uint32_t rrf_k, uint64_t filter_id, float* out_scores, uint64_t* out_rows,
+                    uint32_t* out_count) {
+  if (!eng) return fail(VS_ERR_INVALID_ARG, "engine is NULL");
+  if (!eng->sharded)
+    return vsd::search_fused_host(eng->dev[0], coll, queries, nq, n_sub, dim, k, prefetch_limit,
+                                  fusion, rrf_k, filter_id, out_scores, out_rows, out_count);
+  if (const int rc = vsd::fuse_args(n_sub, k, &prefetch_limit, fusion, &rrf_k)) return rc;
+  if (nq == 0) return VS_OK;
+  if (!queries) return fail(VS_ERR_INVALID_ARG, "queries is NULL");
+  if (nq > 0xFFFFFFFFu / n_sub)
+    return fail(VS_ERR_INVALID_ARG, "nq * n_sub exceeds 2^32-1 queries");
+  auto sc = find_scoll(eng, coll);
+  if (!sc) return not_found(coll);
+  SFilter f;
+  if (filter_id) {
+    std::lock_guard<std::mutex> g(eng->filt_mu);
+    auto it = eng->filters.find(filter_id);
+    if (it == eng->filters.end())
+      return fail(VS_ERR_NOT_FOUND, "filter " + std::to_string(filter_id) + " not found");
+    f = it->second;
+  }
+  if (sc->home >= 0) {  // placed: the home device's own fused search
+    if (filter_id && f.coll_gen != sc->gen)
+      return fail(VS_ERR_INVALID_ARG, "filter " + std::to_string(filter_id) +
+                                          " was built for another collection state");
+    return vsd::search_fused_host(home_eng(eng, *sc), sc->iname[0].c_str(), queries, nq, n_sub,
+                                  dim, k, prefetch_limit, fusion, rrf_k,
+                                  filter_id ? f.dev_fid[0] : 0, out_scores, out_rows, out_count);
+  }
+  return striped_search_fused_host(eng, *sc, queries, nq, n_sub, dim, k, prefetch_limit, fusion,
+                                   rrf_k, filter_id ? &f : nullptr, filter_id, out_scores,
+                                   out_rows, out_count);
+}
+
+int vs_fuse_keys(vs_engine* eng, const uint64_t* d_lists, uint32_t nq, uint32_t n_sub,
+                 uint32_t k_in, uint32_t k, int fusion, uint32_t rrf_k, uint64_t* d_out_keys,
+                 void* stream) {
+  if (!eng) return fail(VS_ERR_INVALID_ARG, "engine is NULL");
+  if (const int rt = vsd::one_hip_runtime()) return rt;
+  return vsd::fuse_keys(eng->dev[0], d_lists, nq, n_sub, k_in, k, fusion, rrf_k, d_out_keys,
+                        stream);
 }
 
 int vs_grouping_create(vs_engine* eng, const char* coll, const uint32_t* group_of_row,

@@ -301,6 +301,7 @@ struct DevEngine {
   DevBuf small_part;
   DevBuf q8g;  // one query on the int8 copy: workgroup lists, wave bounds, candidates
   DevBuf mmr_cand;  // vs_search_mmr: the candidate search's keys, [nq][candidates_limit]
+  DevBuf fuse_lists;  // vs_search_fused: the candidate lists, [nq][n_sub][prefetch_limit]
   // grouped search: the groups' best keys (zero between calls), the workgroup
   // lists, the returned heads, the answer's group ids [nq][limit]
   DevBuf grp_best, grp_lists, grp_heads, grp_ids;
@@ -389,6 +390,21 @@ int mmr_keys(DevEngine* eng, const char* coll, const uint64_t* d_cand_keys, uint
 // reader lock held by the caller.
 int mmr_core(DevEngine* eng, Collection& c, const uint64_t* d_cand, uint32_t nq, uint32_t n_cand,
              uint32_t k, float diversity, uint64_t* d_out);
+// Fused search (include/vsearch.h states the rule). fuse_args checks n_sub, k,
+// the list length (prefetch_limit or k_in; 0 = the default, resolved in place),
+// the method and rrf_k (RRF's 0 resolved to 2 in place) alone, so every layout
+// reports a bad argument before it looks at the collection.
+int fuse_args(uint32_t n_sub, uint32_t k, uint32_t* limit, int fusion, uint32_t* rrf_k);
+int search_fused_host(DevEngine* eng, const char* coll, const float* queries, uint32_t nq,
+                      uint32_t n_sub, uint32_t dim, uint32_t k, uint32_t prefetch_limit, int fusion,
+                      uint32_t rrf_k, uint64_t filter_id, float* out_scores, uint64_t* out_rows,
+                      uint32_t* out_count);
+int fuse_keys(DevEngine* eng, const uint64_t* d_lists, uint32_t nq, uint32_t n_sub, uint32_t k_in,
+              uint32_t k, int fusion, uint32_t rrf_k, uint64_t* d_out_keys, void* stream);
+// The fusion launch alone on eng->stream (arguments as fuse_args left them);
+// work_mu held by the caller.
+int fuse_core(DevEngine* eng, const uint64_t* d_lists, uint32_t nq, uint32_t n_sub, uint32_t k_in,
+              uint32_t k, int fusion, uint32_t rrf_k, uint64_t* d_out);
 // Grouped search (include/vsearch.h states the rule). groups_args checks limit
 // and group_size alone, so every layout reports them before the collection.
 int groups_args(uint32_t limit, uint32_t group_size);

@@ -2343,6 +2343,160 @@ int mmr_keys(DevEngine* eng, const char* coll, const uint64_t* d_cand_keys, uint
   return mmr_core(eng, *c, d_cand_keys, nq, n_cand, k, diversity, d_out_keys);
 }
 
+// ---- fused search (include/vsearch.h "Fused search") -------------------------
+
+int fuse_args(uint32_t n_sub, uint32_t k, uint32_t* limit, int fusion, uint32_t* rrf_k) {
+  if (n_sub == 0) return fail(VS_ERR_INVALID_ARG, "n_sub must be at least 1");
+  if (n_sub > VS_FUSE_MAX_LISTS)
+    return fail(VS_ERR_INVALID_ARG, "n_sub " + std::to_string(n_sub) +
+                                        " exceeds VS_FUSE_MAX_LISTS " +
+                                        std::to_string(VS_FUSE_MAX_LISTS));
+  if (k == 0) return fail(VS_ERR_INVALID_ARG, "k must be at least 1");
+  if (k > VS_FUSE_MAX_LIMIT)
+    return fail(VS_ERR_INVALID_ARG, "k " + std::to_string(k) + " exceeds VS_FUSE_MAX_LIMIT " +
+                                        std::to_string(VS_FUSE_MAX_LIMIT));
+  uint32_t F = *limit;
+  if (F == 0) F = std::min<uint32_t>(std::max<uint32_t>(4 * k, k), VS_FUSE_MAX_LIMIT);
+  if (F > VS_FUSE_MAX_LIMIT)
+    return fail(VS_ERR_INVALID_ARG, "prefetch_limit " + std::to_string(F) +
+                                        " exceeds VS_FUSE_MAX_LIMIT " +
+                                        std::to_string(VS_FUSE_MAX_LIMIT));
+  if (k > F)
+    return fail(VS_ERR_INVALID_ARG, "k " + std::to_string(k) + " exceeds prefetch_limit " +
+                                        std::to_string(F));
+  if (fusion != VS_FUSION_RRF && fusion != VS_FUSION_DBSF)
+    return fail(VS_ERR_INVALID_ARG, "unknown fusion " + std::to_string(fusion));
+  if (*rrf_k > 65536u)
+    return fail(VS_ERR_INVALID_ARG, "rrf_k " + std::to_string(*rrf_k) + " exceeds 65536");
+  if (fusion == VS_FUSION_DBSF && *rrf_k != 0)
+    return fail(VS_ERR_INVALID_ARG, "rrf_k must be 0 with VS_FUSION_DBSF");
+  if (fusion == VS_FUSION_RRF && *rrf_k == 0) *rrf_k = 2;
+  *limit = F;
+  return VS_OK;
+}
+
+int fuse_core(DevEngine* eng, const uint64_t* d_lists, uint32_t nq, uint32_t n_sub, uint32_t k_in,
+              uint32_t k, int fusion, uint32_t rrf_k, uint64_t* d_out) {
+  VS_HIP(vsk::launch_fuse(d_lists, nq, n_sub, k_in, k, fusion == VS_FUSION_DBSF, rrf_k, d_out,
+                          eng->stream),
+         "fuse");
+  return VS_OK;
+}
+
+// search_mmr_host with the fusion stage in the selection's place: the nq * n_sub
+// sub-queries are searched as ONE batch into a context buffer, fused there, and
+// only k keys per fused query come back. The reader lock spans both stages.
+int search_fused_host(DevEngine* eng, const char* coll, const float* queries, uint32_t nq,
+                      uint32_t n_sub, uint32_t dim, uint32_t k, uint32_t prefetch_limit, int fusion,
+                      uint32_t rrf_k, uint64_t filter_id, float* out_scores, uint64_t* out_rows,
+                      uint32_t* out_count) {
+  if (!eng) return fail(VS_ERR_INVALID_ARG, "engine is NULL");
+  const int arc = fuse_args(n_sub, k, &prefetch_limit, fusion, &rrf_k);
+  if (arc != VS_OK) return arc;
+  if (nq == 0) return VS_OK;
+  if (!queries) return fail(VS_ERR_INVALID_ARG, "queries is NULL");
+  if (nq > 0xFFFFFFFFu / n_sub)
+    return fail(VS_ERR_INVALID_ARG, "nq * n_sub exceeds 2^32-1 queries");
+  auto c = find_coll(eng, coll);
+  if (!c) return fail(VS_ERR_NOT_FOUND, std::string("collection ") + (coll ? coll : "") +
+                                            " not found");
+  if (dim != c->dim)
+    return fail(VS_ERR_DIM_MISMATCH, "Vector dimension error: expected dim: " +
+                                         std::to_string(c->dim) + ", got " + std::to_string(dim));
+  std::shared_lock<std::shared_mutex> rl(c->mu);
+  // the candidate search is sized for min(F, rows), the fusion for min(k, that);
+  // the caller's outputs keep their stride k
+  const uint32_t ko = k, nsq = nq * n_sub;
+  const uint32_t F = (uint32_t)std::min<uint64_t>(prefetch_limit, std::max<uint64_t>(c->rows, 1));
+  k = std::min(k, F);
+  std::shared_ptr<DevFilter> df;
+  if (filter_id) {
+    df = find_filter(eng, filter_id);
+    if (!df) return fail(VS_ERR_NOT_FOUND, "filter " + std::to_string(filter_id) + " not found");
+    if (df->coll_gen != c->gen || df->rows != c->rows)
+      return fail(VS_ERR_INVALID_ARG, "filter " + std::to_string(filter_id) +
+                                          " was built for another collection state");
+  }
+  std::unique_lock<std::mutex> g;
+  DevEngine* cx = pick_context(eng, &g, heavy_search(*c, nsq));
+  cx->inflight.fetch_add(1, std::memory_order_relaxed);
+  struct Leave {
+    DevEngine* cx;
+    ~Leave() { cx->inflight.fetch_sub(1, std::memory_order_relaxed); }
+  } leave{cx};
+  VS_HIP(set_dev(cx), "hipSetDevice");
+  VS_HIP(use_stream(cx, cx->own), "stream order");
+  const size_t qbytes = (size_t)nsq * c->dim * 4;
+  const size_t kbytes = (size_t)nq * k * 8;
+  const size_t lbytes = (size_t)nsq * F * 8;
+  if (cx->q_in.bytes < qbytes || cx->keys.bytes < kbytes || cx->fuse_lists.bytes < lbytes) {
+    VS_HIP(hipStreamSynchronize(cx->stream), "sync");
+    VS_HIP(cx->q_in.ensure(qbytes), "alloc query input");
+    VS_HIP(cx->keys.ensure(kbytes), "alloc keys");
+    VS_HIP(cx->fuse_lists.ensure(lbytes), "alloc fusion lists");
+  }
+  HostSlot* hs = nullptr;
+  for (auto& x : cx->host_slots)
+    if (!x->busy) {
+      hs = x.get();
+      break;
+    }
+  if (!hs) {
+    cx->host_slots.push_back(std::make_unique<HostSlot>());
+    hs = cx->host_slots.back().get();
+  }
+  VS_HIP(hs->ensure(qbytes, kbytes), "alloc pinned staging");
+  std::memcpy(hs->in, queries, qbytes);
+  hs->busy = true;
+  auto abandon = [&](int rc) {
+    (void)hipStreamSynchronize(cx->stream);
+    hs->busy = false;
+    return rc;
+  };
+  hipError_t e = hipMemcpyAsync(cx->q_in.p, hs->in, qbytes, hipMemcpyHostToDevice, cx->stream);
+  if (e != hipSuccess) return abandon(fail_hip(e, "query H2D"));
+  int rc;
+  if (df)
+    rc = search_core(cx, *c, cx->q_in.as<float>(), nsq, F, cx->fuse_lists.as<uint64_t>(),
+                     df->bits.as<uint64_t>(), df->allowed,
+                     df->list.p ? df->list.as<uint32_t>() : nullptr);
+  else
+    rc = search_core(cx, *c, cx->q_in.as<float>(), nsq, F, cx->fuse_lists.as<uint64_t>());
+  if (rc == VS_OK)
+    rc = fuse_core(cx, cx->fuse_lists.as<uint64_t>(), nq, n_sub, F, k, fusion, rrf_k,
+                   cx->keys.as<uint64_t>());
+  if (rc != VS_OK) return abandon(rc);
+  e = hipMemcpyAsync(hs->out, cx->keys.p, kbytes, hipMemcpyDeviceToHost, cx->stream);
+  if (e == hipSuccess) e = hipEventRecord(hs->done, cx->stream);
+  if (e != hipSuccess) return abandon(fail_hip(e, "keys D2H"));
+  g.unlock();  // wait outside work_mu, as search_host does
+  const hipError_t we = wait_event(hs->done);
+  if (we == hipSuccess)
+    decode_host((const uint64_t*)hs->out, nq, k, out_scores, out_rows, out_count, ko);
+  g.lock();
+  hs->busy = false;
+  VS_HIP(we, "search sync");
+  return VS_OK;
+}
+
+int fuse_keys(DevEngine* eng, const uint64_t* d_lists, uint32_t nq, uint32_t n_sub, uint32_t k_in,
+              uint32_t k, int fusion, uint32_t rrf_k, uint64_t* d_out_keys, void* stream) {
+  if (!eng) return fail(VS_ERR_INVALID_ARG, "engine is NULL");
+  if (k_in == 0) return fail(VS_ERR_INVALID_ARG, "k_in must be at least 1");
+  const int arc = fuse_args(n_sub, k, &k_in, fusion, &rrf_k);
+  if (arc != VS_OK) return arc;
+  if (nq == 0) return VS_OK;
+  if (!d_lists || !d_out_keys) return fail(VS_ERR_INVALID_ARG, "NULL device pointer");
+  std::lock_guard<std::mutex> g(eng->work_mu);
+  VS_HIP(set_dev(eng), "hipSetDevice");
+  // the stage has no scratch of its own: it runs directly on the caller's
+  // stream, as the list merge of vs_merge_keys does
+  hipError_t e = vsk::launch_fuse(d_lists, nq, n_sub, k_in, k, fusion == VS_FUSION_DBSF, rrf_k,
+                                  d_out_keys, (hipStream_t)stream);
+  if (e != hipSuccess) return fail_hip(e, "fuse");
+  return VS_OK;
+}
+
 // ---- grouped search (include/vsearch.h "Grouped search") --------------------
 
 int groups_args(uint32_t limit, uint32_t group_size) {

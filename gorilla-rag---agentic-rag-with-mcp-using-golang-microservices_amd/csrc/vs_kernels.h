@@ -521,6 +521,19 @@ hipError_t launch_group_members(const uint32_t* sc, const uint32_t* gid, const u
                                 uint64_t* lists, uint32_t* groups, hipStream_t st);
 hipError_t launch_group_clear(uint64_t* best, uint32_t n_groups, hipStream_t st);
 
+// Fused search (vs_fuse.hip; include/vsearch.h "Fused search"). lists is
+// [nq][n_sub][k_in] keys as vs_search_keys writes them (0 = an empty slot); out
+// is [nq][k] keys carrying the fused score, descending, 0 past min(k, distinct
+// rows). 1 <= n_sub <= kFuseMaxLists, 1 <= k <= k_in <= kFuseMaxLimit; RRF takes
+// 1 <= rrf_k <= 65536 (the caller resolves the default), DBSF rrf_k == 0. One
+// workgroup per fused query, all of it in LDS: two bitonic sorts around a
+// sequential walk of every row's run, which fixes the fp32 summation order.
+// lists and out must not overlap. Nothing but the two arrays is touched.
+constexpr uint32_t kFuseMaxLists = 8;
+constexpr uint32_t kFuseMaxLimit = kMfmaMaxK;
+hipError_t launch_fuse(const uint64_t* lists, uint32_t nq, uint32_t n_sub, uint32_t k_in,
+                       uint32_t k, bool dbsf, uint32_t rrf_k, uint64_t* out, hipStream_t st);
+
 int device_cu_count();
 
 }  // namespace vsk

@@ -55,11 +55,16 @@ EXPORTS = (
     "vs_collection_prefilter_bytes", "vs_collection_spec_stats", "vs_delete",
     "vs_search_mmr", "vs_mmr_keys",
     "vs_grouping_create", "vs_grouping_drop", "vs_search_groups", "vs_group_keys",
+    "vs_search_fused", "vs_fuse_keys",
 )
 MMR_MAX_CANDIDATES = 128
 GROUP_NONE = 0xFFFFFFFF
 GROUPS_MAX_LIMIT = 128
 GROUPS_MAX_SIZE = 16
+FUSION_RRF = 0
+FUSION_DBSF = 1
+FUSE_MAX_LISTS = 8
+FUSE_MAX_LIMIT = 128
 COMM_ID_BYTES = 128
 
 
@@ -168,6 +173,8 @@ def load_library(path: str = LIB_PATH):
         "vs_grouping_drop": ([vp, u64], i32),
         "vs_search_groups": ([vp, cp, vp, u32, u32, u32, u32, u64, u64, vp, vp, vp, vp, vp], i32),
         "vs_group_keys": ([vp, cp, vp, u32, u32, u32, u32, u64, u64, vp, vp, vp], i32),
+        "vs_search_fused": ([vp, cp, vp, u32, u32, u32, u32, u32, i32, u32, u64, vp, vp, vp], i32),
+        "vs_fuse_keys": ([vp, vp, u32, u32, u32, u32, i32, u32, vp, vp], i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -501,6 +508,34 @@ class VectorEngine:
                                      limit, group_size, grouping_id, filter_id,
                                      ctypes.c_void_p(d_keys), ctypes.c_void_p(d_groups),
                                      ctypes.c_void_p(stream)))
+
+    def search_fused(self, name: str, queries: np.ndarray, k: int, prefetch_limit: int = 0,
+                     fusion: int = FUSION_RRF, rrf_k: int = 0, filter_id: int = 0):
+        """vs_search_fused: `queries` is [nq, n_sub, dim] (or [n_sub, dim] for one
+        fused query); the n_sub sub-queries of each are searched for
+        `prefetch_limit` (0: min(4 k, 128)) rows as one batch and their lists
+        fused on the device (FUSION_RRF with `rrf_k`, 0 = 2; or FUSION_DBSF).
+        Scores are the FUSED scores; `filter_id` (0: none) is a filter made by
+        filter_create."""
+        q = np.ascontiguousarray(queries, np.float32)
+        if q.ndim == 2:
+            q = q[None, :, :]
+        nq, n_sub, dim = q.shape
+        scores = np.zeros((nq, k), np.float32)
+        rows = np.zeros((nq, k), np.uint64)
+        count = np.zeros(nq, np.uint32)
+        _check(self._L.vs_search_fused(self._h, name.encode(), _p(q), nq, n_sub, dim, k,
+                                       prefetch_limit, fusion, rrf_k, filter_id, _p(scores),
+                                       _p(rows), _p(count)))
+        return scores, rows, count
+
+    def fuse_keys(self, d_lists: int, nq: int, n_sub: int, k_in: int, k: int, fusion: int,
+                  rrf_k: int, d_out_keys: int, stream: int = 0):
+        """vs_fuse_keys: the fusion stage alone over device lists ([nq][n_sub][k_in]
+        keys as search_keys writes them) -> [nq][k] keys carrying the fused
+        score, descending, on `stream`."""
+        _check(self._L.vs_fuse_keys(self._h, ctypes.c_void_p(d_lists), nq, n_sub, k_in, k, fusion,
+                                    rrf_k, ctypes.c_void_p(d_out_keys), ctypes.c_void_p(stream)))
 
     def search_keys(self, name: str, d_queries: int, nq: int, dim: int, k: int, d_keys: int,
                     stream: int = 0):

@@ -314,7 +314,7 @@ int vs_search_filter_id(vs_engine* eng, const char* coll, const float* queries, 
  * The stream and the pointers must come from the HIP runtime this library
  * is linked to: in a process that maps two libamdhip64 runtimes (e.g.
  * torch's bundled copy next to /opt/rocm's) this call and every other one
- * taking caller device pointers (vs_mmr_keys, vs_group_keys, vs_merge_keys, vs_gather_merge_keys,
+ * taking caller device pointers (vs_mmr_keys, vs_group_keys, vs_fuse_keys, vs_merge_keys, vs_gather_merge_keys,
  * vs_decode_keys, vs_generate_vectors) fail with VS_ERR_DEVICE rather than
  * run unordered with the caller's work. vs_runtime_check() runs that test
  * alone (no device needed): VS_OK, or VS_ERR_DEVICE naming both runtimes. */
@@ -452,6 +452,70 @@ int vs_search_groups(vs_engine* eng, const char* coll, const float* queries, uin
 int vs_group_keys(vs_engine* eng, const char* coll, const float* d_queries, uint32_t nq,
                   uint32_t dim, uint32_t limit, uint32_t group_size, uint64_t grouping_id,
                   uint64_t filter_id, uint64_t* d_keys, uint32_t* d_groups, void* stream);
+
+/* ---- Fused search (several sub-queries per question, fused on the device) ----
+ *
+ * Qdrant's query API `prefetch` + `fusion` (rrf, dbsf). The reference's
+ * orchestrator asks its planner for several rewritings of one question
+ * (agent/orchestrator-service/main.go:60) and then searches with one of them
+ * (:531-568); this searches with all of them as one batch and combines the
+ * ranked lists without the lists leaving the device.
+ *
+ * One fused query has n_sub sub-queries, 1 <= n_sub <= VS_FUSE_MAX_LISTS.
+ * Sub-query l yields a list L_l of k_in keys in the form vs_search_keys writes:
+ * sorted descending, no repeats, 0-padded; 1 <= k_in <= VS_FUSE_MAX_LIMIT (the
+ * batched candidate pass's largest k). A key of 0 is an empty slot and
+ * contributes nothing. The rank p of an entry is its slot index, from 0; n_l is
+ * the number of non-zero keys of L_l.
+ *
+ * Every row r found in at least one list gets a fused score: an fp32 sum of one
+ * term per list that holds r, the terms added in ASCENDING l, starting from the
+ * first term (not from 0), each addition rounded once. The order is part of the
+ * contract: another order changes the last bit of some sums.
+ *   VS_FUSION_RRF:  term = 1.0f / (float)(p + K), a correctly rounded fp32
+ *     division; K = rrf_k, 1 <= K <= 65536, rrf_k == 0 means 2.
+ *   VS_FUSION_DBSF (distribution-based score fusion): per list, in fp64 over
+ *     its n_l scores s (vs_key_score of each key): the mean mu, the sample
+ *     variance sum((s - mu)^2) / (n_l - 1) (two passes, any summation order)
+ *     and sigma = sqrt(variance). If n_l == 1 or sigma == 0 every entry's term
+ *     is 0.5f; otherwise term = (float)(((double)s - (mu - 3 sigma)) /
+ *     (6 sigma)), each fp64 operation rounded once and the quotient rounded to
+ *     fp32 once. rrf_k must be 0.
+ * The answer is the min(k, distinct rows) rows with the largest
+ * vs_key_encode(fused, row), descending: fused score descending, equal fused
+ * scores by the lower row. 1 <= k <= 128. Result keys carry the FUSED score (a
+ * row's relevance is one value per list and is not returned); slots past the
+ * count are 0.
+ *  - A result list is sorted descending: a valid input for vs_decode_keys, and
+ *    for vs_mmr_keys (relevance is then the fused score). It is NOT a valid
+ *    input for vs_merge_keys across shards (ranks are per list, so fusion must
+ *    see global lists), nor for a second fusion.
+ *  - A row repeated inside one list (vs_search_keys never writes one): the
+ *    result is unspecified; the call neither faults nor writes outside its
+ *    output.
+ *  - Fusion reads keys, never rows, so vs_search_fused serves every layout:
+ *    vs_open engines, placed collections, and row-striped collections (the
+ *    global candidate search runs as vs_search's does, the fusion on the first
+ *    device). It holds the collection's reader lock throughout. */
+#define VS_FUSE_MAX_LISTS 8u
+#define VS_FUSE_MAX_LIMIT 128u
+typedef enum vs_fusion { VS_FUSION_RRF = 0, VS_FUSION_DBSF = 1 } vs_fusion;
+/* queries: [nq][n_sub][dim] fp32. The lists of fused query i are exactly the
+ * keys vs_search returns for these nq * n_sub queries AS ONE BATCH with
+ * k = prefetch_limit (under filter_id when != 0). prefetch_limit == 0 means
+ * min(max(4 k, k), 128); k <= prefetch_limit <= VS_FUSE_MAX_LIMIT. Outputs have
+ * stride k, zero past out_count[i]. nq == 0 returns VS_OK. */
+int vs_search_fused(vs_engine* eng, const char* coll, const float* queries, uint32_t nq,
+                    uint32_t n_sub, uint32_t dim, uint32_t k, uint32_t prefetch_limit,
+                    int fusion, uint32_t rrf_k, uint64_t filter_id, float* out_scores,
+                    uint64_t* out_rows, uint32_t* out_count);
+/* The fusion stage alone: d_lists [nq][n_sub][k_in] -> d_out_keys [nq][k],
+ * 1 <= k <= k_in. The two must not overlap. No collection is involved. Ordered
+ * on `stream` under the one-runtime rule (vs_runtime_check), as vs_merge_keys
+ * is. */
+int vs_fuse_keys(vs_engine* eng, const uint64_t* d_lists, uint32_t nq, uint32_t n_sub,
+                 uint32_t k_in, uint32_t k, int fusion, uint32_t rrf_k, uint64_t* d_out_keys,
+                 void* stream);
 
 /* Merges `n_lists` per-shard key lists into the global top-k on the device:
  * d_lists is [n_lists][nq][k_in] (e.g. the result of an all-gather of

@@ -79,6 +79,28 @@
  * 501 when the engine library lacks vs_search_groups, vs_grouping_create or
  * vs_grouping_drop (referenced weakly).
  *
+ * /search also takes "fusion": {"method": "rrf"|"dbsf", "queries": [[...], ...],
+ * "prefetch_limit": integer, "rrf_k": integer} (Qdrant's query-API prefetch +
+ * fusion; include/vsearch.h "Fused search"): several phrasings of one question
+ * searched as one batch and their ranked lists fused on the device. The
+ * request's own "query" is sub-query 0 and "queries" holds 1 to 7 more vectors,
+ * so the reference service, which ignores unknown fields, answers the same body
+ * with the plain search of "query". "method" defaults to "rrf", "prefetch_limit"
+ * to 0 (the engine's min(4 top_k, 128)) and "rrf_k" to 0 (the engine's 2); a
+ * null field keeps its default and a null or absent "fusion" leaves the route
+ * exactly as it is. 400 "Invalid request body": a "fusion" that is not an
+ * object, a field of the wrong type, an unknown method, "queries" absent, empty
+ * or longer than 7, a prefetch_limit outside [0, 128], an rrf_k outside
+ * [0, 65536] or given with "dbsf", and "fusion" together with "mmr" or
+ * "group_by". Each extra vector then passes convertVector's rules (400 with its
+ * texts) and must have the collection's dim (500 with the dimension error of
+ * "query"). top_k is clamped to the collection's rows as always and must then
+ * be at most 128 (else 400); prefetch_limit is raised to at least that; and the
+ * request goes straight to vs_search_fused with nq = 1 (not through the
+ * batcher), under the resident filter when "filter":"match" is configured and a
+ * filter is given. The reply has the same shape; "score" is the FUSED score.
+ * 501 when the engine library has no vs_search_fused (referenced weakly).
+ *
  * Point UUIDs and payloads live here (a UUID -> row map and a row-indexed
  * payload store per collection); the engine sees dense rows only. A Go
  * deployment binds the same engine C-ABI through cgo and
